@@ -6,15 +6,26 @@ gait schedule + x_init update, warm start, sqp_data (node evaluation and dual
 Jacobians), OSQP update (Ruiz scaling + block KKT factor), ADMM (<= 100 iterations,
 termination checks every 25), Armijo/filter line search and the state update
 x <- integrate(x, DX[1]) (run_mpc.py:127-143).  Inputs are resident in HBM when
-the timed region starts; nothing crosses PCIe inside it.  A second, shorter timed pass
-adds the per-step download of the controller output [u_0, x_state] (the "host_io" object:
-the PCIe-inclusive rate, never `value`).
+the timed region starts; nothing crosses PCIe inside it.
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds
+what else the benchmark measures, each a run of its own: the CPU baseline (before the
+GPU is initialised), a second, shorter timed pass with the per-step download of the
+controller output [u_0, x_state] (the "host_io" object: the PCIe-inclusive rate, never
+`value`), and, for batches below 64, the profiled steps the roofline is taken from.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the MPC loop
+receives it, to DIR/<name>.npy (float64): u0_xstate [problems][nu_0 + nx] (pl_mpc_download)
+and step_stats [problems][4] (status, solver iterations, line-search step, objective);
+above 64 MB in all, a fixed seeded sample of the problems.
+The inputs are seeded by the problem index, so two runs with the same arguments solve the
+same problems.
 
 Multi-GPU: one process per GPU (torchrun), problems [rank*B, (rank+1)*B) with
 seeds from the global problem index (weak scaling, no data-path collective); the
 per-problem results are all-gathered over RCCL after the timed region.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torchrun environment, bench.py launches the N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU) and
@@ -44,6 +55,7 @@ from pinoloco.synthetic import build_batch, shard  # noqa: E402
 
 METRIC = "MPC solves/sec (B2G whole_body_rnea N=50) at batch; 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s)
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all arrays together
 
 
 TRAFFIC_FILE = os.path.join(HERE, "profiles", "traffic", "admm_traffic.json")
@@ -229,6 +241,45 @@ def cpu_baseline_ip(robot, dynamics, N, per_core=1):
             "cgroup_cpu_quota": _cgroup_cpu_quota()}
 
 
+def admm_roofline(bo, lay, prof, B, nodes, workload, prof_timed):
+    """The HBM roofline of the ADMM kernel from the per-launch event times `prof` (pl_ocp_profile)."""
+    kernel = bo.admm_kernel()
+    kname = {"sweep": "k_admm", "sweep2": "k_admm2", "chain": "k_admm_rc"}[kernel]
+    sz = bo.sizes()
+    ntab = bo.node_table()
+    bytes_it = admm_bytes_per_problem_iter(sz, ntab, kernel=kernel, ndx=lay.ndx)
+    bytes_it_padded = admm_bytes_per_problem_iter(sz, ntab, padded=True, kernel=kernel, ndx=lay.ndx)
+    iters_per_launch = prof["problem_iters"] / max(1, prof["launches"])
+    per_launch_bytes = bytes_it * iters_per_launch
+    avg_launch_s = prof["admm_ms"] / max(1, prof["launches"]) / 1e3
+    achieved = per_launch_bytes / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+    tj = measured_traffic(B, nodes, workload) if kernel == "sweep" else None
+    # PMC bytes per problem-iteration x this run's problem-iterations per launch
+    traffic = tj["bytes_per_problem_iter"] * iters_per_launch if tj else None
+    return {"bound": "hbm", "kernel": kname, "byte_model": kernel, "workgroups_per_problem": bo.admm_groups(),
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "algorithmic_bytes_per_launch": per_launch_bytes,
+            "bytes_per_problem_iter": bytes_it, "bytes_per_problem_iter_padded": bytes_it_padded,
+            "problem_iters_per_launch": iters_per_launch, "avg_launch_ms": avg_launch_s * 1e3,
+            "launches": prof["launches"],
+            "launch_timing": "timed region" if prof_timed else "profiled steps after the timed region (graph replay in it)",
+            "traffic_source": (f"profiles/traffic/admm_traffic.json (k_admm src {tj['src_sha']})" if tj else None)}
+
+
+def step_outputs(bo, solver):
+    """What a caller of the MPC loop receives after a step, per problem: the controller output
+    [u_0, x_state] and [status, solver iterations, line-search step, objective] of its solve."""
+    if solver == "fatrop":
+        st = bo.ip_stats()
+        cols = [st["status"], st["iter"], st["alpha"], st["f"]]
+    else:
+        st = bo.mpc_stats()
+        cols = [st["status"], st["admm_iters"], st["ls_alpha"], st["f"]]
+    return {"u0_xstate": bo.mpc_download(), "step_stats": np.stack([np.asarray(c, dtype=np.float64) for c in cols], 1)}
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -278,7 +329,11 @@ def main():
     ap.add_argument("--robot", default="b2g")
     ap.add_argument("--dynamics", default="whole_body_rnea")
     ap.add_argument("--nodes", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the host_io pass and, below batch 64, the roofline's profiled steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--solver", default="osqp", choices=["osqp", "fatrop"],
                     help="osqp: the headline SQP + OSQP path; fatrop: the interior-point restatement")
     ap.add_argument("--dry-run", action="store_true", help="gloo plumbing only, no GPU")
@@ -287,9 +342,14 @@ def main():
     ap.add_argument("--debug-paths", default="",
                     help="comma list of pl_ocp_desc.debug_paths names (earlier kernel paths, A/B runs only)")
     ap.add_argument("--host-io-steps", type=int, default=None,
-                    help="extra steps timed with the per-step D2H of [u_0, x_state] (default min(steps, 10))")
+                    help="with --full: extra steps timed with the per-step D2H of [u_0, x_state] "
+                         "(default min(steps, 10))")
     args = ap.parse_args()
-    if args.host_io_steps is None:
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.host_io_steps = 0
+    elif args.host_io_steps is None:
         args.host_io_steps = min(args.steps, 10)
 
     world, rank, local_rank = pdist.env_ranks()
@@ -300,7 +360,7 @@ def main():
     if args.dry_run:
         return dry_run(args, world, rank)
     base = None
-    if not args.no_cpu_baseline and world == 1:  # before the GPU is initialised
+    if args.full and not args.no_cpu_baseline and world == 1:  # before the GPU is initialised
         if args.solver == "osqp":
             base = cpu_baseline(args.robot, args.dynamics, args.nodes)
         else:
@@ -335,7 +395,8 @@ def main():
     # Per-launch HIP events on the ADMM launches (the roofline's avg_launch_ms) are taken
     # over the timed region itself for batches >= 64.  A latency-bound small batch replays
     # each MPC step as one HIP graph (pl_mpc_step), which per-launch events would disable:
-    # there the ADMM launches are timed over the same number of profiled steps right after.
+    # there the ADMM launches are timed over the same number of profiled steps right after
+    # (a run of its own: --full only, a plain run of such a batch prints no roofline).
     prof_timed = args.batch >= 64
     for k in range(args.warmup):
         bo.mpc_step(k)
@@ -364,15 +425,23 @@ def main():
             bo.mpc_step(k)
         barrier_sync()
         elapsed = time.perf_counter() - t0
-    if not prof_timed:
+    # the outputs of the last timed step, read before any later pass steps the loop on
+    dump = step_outputs(bo, args.solver) if args.dump_outputs else None
+    if not prof_timed and args.full:
         bo.profile(1)
         for k in range(args.warmup + args.steps, args.warmup + 2 * args.steps):
             bo.mpc_step(k)
         bo.sync()
-    prof = bo.profile_read()
-    hprof = bo.profile_read_hess() if args.solver == "fatrop" else None  # read before profile(0) clears
-    bo.profile(0)
+    prof = hprof = None
+    if prof_timed or args.full:
+        prof = bo.profile_read()
+        hprof = bo.profile_read_hess() if args.solver == "fatrop" else None  # read before profile(0) clears
+        bo.profile(0)
     elapsed = pdist.max_over_ranks(elapsed, dist)
+    if dump is not None and dist is not None:
+        import torch
+        dump = {name: pdist.gather_rows(torch.from_numpy(a).to(f"cuda:{local_rank}"), dist).cpu().numpy()
+                for name, a in dump.items()}
     if dist is not None:
         # per-problem controller output [u_0, x_state] of the whole job, gathered over
         # RCCL after the timed region (no collective on the data path)
@@ -405,20 +474,10 @@ def main():
                    "what": "per step: pl_mpc_step + pl_mpc_download ([u_0, x_state] of every problem to "
                            "host memory) + wait; inputs resident, the state stays on the device"}
 
-    kernel = bo.admm_kernel()
-    kname = {"sweep": "k_admm", "sweep2": "k_admm2", "chain": "k_admm_rc"}[kernel]
-    sz = bo.sizes()
-    ntab = bo.node_table()
-    bytes_it = admm_bytes_per_problem_iter(sz, ntab, kernel=kernel, ndx=lay.ndx)
-    bytes_it_padded = admm_bytes_per_problem_iter(sz, ntab, padded=True, kernel=kernel, ndx=lay.ndx)
-    iters_per_launch = prof["problem_iters"] / max(1, prof["launches"])
-    per_launch_bytes = bytes_it * iters_per_launch
-    avg_launch_s = prof["admm_ms"] / max(1, prof["launches"]) / 1e3
-    achieved = per_launch_bytes / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
     workload = f"{args.robot} {args.dynamics} N={args.nodes} MPC step"
-    tj = measured_traffic(B, args.nodes, workload) if kernel == "sweep" else None
-    # PMC bytes per problem-iteration x this run's problem-iterations per launch
-    traffic = tj["bytes_per_problem_iter"] * iters_per_launch if tj else None
+    roofline = None
+    if prof is not None:
+        roofline = admm_roofline(bo, lay, prof, B, args.nodes, workload, prof_timed)
 
     if rank == 0:
         total = B * world * args.steps
@@ -441,16 +500,6 @@ def main():
                        "solver": ("osqp-sqp (1 SQP iteration, max_iter 100)" if args.solver == "osqp" else
                                   "fatrop-equivalent interior point (max_iter 10, tol 1e-3, mu_init 1e-4)"),
                        "parallelism": f"batch-sharded dp{world}", **({"debug_paths": list(paths)} if paths else {})},
-            "roofline": {"bound": "hbm", "kernel": kname, "byte_model": kernel, "workgroups_per_problem": bo.admm_groups(),
-                         "achieved": achieved,
-                         "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": per_launch_bytes,
-                         "bytes_per_problem_iter": bytes_it, "bytes_per_problem_iter_padded": bytes_it_padded,
-                         "problem_iters_per_launch": iters_per_launch, "avg_launch_ms": avg_launch_s * 1e3,
-                         "launches": prof["launches"], "launch_timing": "timed region" if prof_timed else "profiled steps after the timed region (graph replay in it)",
-                         "traffic_source": (f"profiles/traffic/admm_traffic.json (k_admm src {tj['src_sha']})"
-                                            if tj else None)},
         }
         from pinoloco import _lib as plib
         from pinoloco import build as pbuild
@@ -461,7 +510,9 @@ def main():
             out["host_io"] = host_io
         if base is not None:
             out["cpu_baseline"] = base
-        if args.solver == "fatrop":
+        if roofline is not None:
+            out["roofline"] = roofline
+        if args.solver == "fatrop" and hprof is not None:
             # the IP step's dominant kernel is the Lagrangian Hessian (FP64 VALU-bound): its own
             # roofline; the ADMM sweeps' HBM line above moves to admm_roofline
             hp = hprof
@@ -484,6 +535,7 @@ def main():
                                "active_lane_fraction": lane_frac,
                                "flops_source": (f"profiles/traffic/hess_flops.json (PMC F64 instruction counts, "
                                                 f"src {hf['src_sha']})" if hf else None)}
+        if args.solver == "fatrop":
             tot = {}
             for st_ in ip_steps:
                 for a, c in st_["status_counts"].items():
@@ -493,6 +545,16 @@ def main():
                                "status_counts_timed": tot, "frac_ls_failed": tot.get(-2, 0) / max(1, sum(tot.values())),
                                "converged_or_max_iter_solves_per_s": ok * world / elapsed,
                                "per_step": ip_steps}
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            rows = B * world
+            cap = DUMP_MAX_BYTES // (8 * sum(a.shape[1] for a in dump.values()))
+            if rows > cap:  # a fixed, seeded sample of the problems (the same rows of every array)
+                keep = np.sort(np.random.default_rng(0).choice(rows, cap, replace=False))
+                dump = {name: a[keep] for name, a in dump.items()}
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+            out["outputs"] = {name: list(a.shape) for name, a in dump.items()}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -9,9 +9,9 @@ import os
 import numpy as np
 import pytest
 
-from conftest import make_robot
+from conftest import GOLDEN, make_robot
 
-REF = "/root/reference"
+REF = GOLDEN  # robots/<name>_description/{urdf,srdf}/: the reference's robot descriptions
 
 
 @pytest.mark.parametrize("name,nq,nv,mass", [("go2", 19, 18, 16.087), ("b2", 19, 18, 72.5803),
@@ -56,9 +56,9 @@ def test_json_roundtrip():
     assert m2.total_mass() == pytest.approx(R.model.total_mass(), rel=1e-15)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference URDFs only in the build container")
 def test_tables_regenerate_from_urdf():
-    """The shipped JSON tables equal a fresh parse of the reference URDF/SRDF."""
+    """The shipped JSON tables equal a fresh parse of the reference URDF/SRDF (stored as data
+    under tests/golden/robots/)."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
     import gen_models
