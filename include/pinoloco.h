@@ -260,6 +260,37 @@ int pl_mpc_export(pl_ocp* o, void* device_dst);
  * run_mpc.py:138-141 reads: u_0 and the next state).  bench.py times it beside the step
  * for the PCIe-inclusive rate. */
 int pl_mpc_download(pl_ocp* o, double* host_dst);
+/* Batched retract of the solved horizon on the device: per problem and node the configuration q,
+ * velocity v, acceleration a, contact forces, joint torques tau and eom_base, the base rows of
+ * RNEA(q, v, a, forces) (the tau_b whose norm run_mpc.py:232-236 prints).  It is what
+ * retract_stacked_sol returns after every solve (optimization/ocp.py:422,
+ * ocp_whole_body_rnea.py:293-324, ocp_whole_body_acc.py:195-234, ocp_whole_body_aba.py:177-214,
+ * ocp_centroidal_vel.py:195-260), compile_solution exports for the hardware
+ * (ocp_whole_body_rnea.py:326-366) and run_mpc.py:186-241 recomputes per node, from the
+ * handle's current iterate and each problem's own parameters (x_init, step sizes).  steps in
+ * [1, N] nodes from node 0; terminal = 1 (needs steps == N) adds node N's row to q and, where v is
+ * part of the state, to v (centroidal_vel: v comes from the inputs, its row count stays steps).
+ * Rules the reference's three-node export never reaches: centroidal_vel's node N - 1 reuses the
+ * previous node's velocity difference (there is no U[N]); whole_body_rnea nodes without a tau
+ * variable (i >= tau_nodes) return the RNEA joint rows (run_mpc.py:211, 233), so tau is always
+ * nj wide; whole_body_rnea with include_acc = 0 keeps a 0 columns wide and uses
+ * a = (v_{i+1} - v_i) / dt_i inside RNEA (ocp_whole_body_rnea.py:183-191).
+ * Valid after pl_ocp_solve and after pl_mpc_step alike: after an MPC step the parameters still
+ * hold that step's x_init and the iterate its solution, so there is no pl_mpc_* variant.  A
+ * problem that did not converge retracts its current iterate.  pl_mpc_step never launches it.
+ *
+ * pl_ocp_retract_sizes: out[19] = for each field in the order q, v, a, forces, tau, eom_base
+ * its width, row count and offset (doubles) in the packed result, then the total number of
+ * doubles of the whole batch.  The packed result is field-major, each field
+ * [batch][rows][width].  Works on a handle without a device. */
+int pl_ocp_retract_sizes(const pl_ocp* o, int steps, int terminal, long long* out /*[19]*/);
+/* The fields into caller-owned HOST arrays [batch][rows][width] (any may be NULL: not copied),
+ * through a pinned staging buffer of the handle; returns after the copies landed. */
+int pl_ocp_retract(pl_ocp* o, int steps, int terminal, double* q, double* v, double* a, double* forces,
+                   double* tau, double* eom_base);
+/* The packed result into a caller-owned DEVICE buffer of out[18] doubles; synchronises the
+ * handle's stream before returning, as pl_mpc_export does. */
+int pl_ocp_retract_device(pl_ocp* o, int steps, int terminal, void* device_dst);
 /* MPC-step HIP graph state: out[0] captures, out[1] graph launches, out[2] = 1 when the
  * step fell back to eager launches (a capture or replay failed, or PL_MPC_GRAPH=0). */
 int pl_mpc_graph_info(const pl_ocp* o, long long* out);

@@ -7,6 +7,7 @@
 // (optimization/ocp.py:38-44, 103-198, 283, 305) and the device programs are built in
 // api_build.hip; the CasADi external-function ABI is api_casadi.hip.
 #include "api_internal.h"
+#include "retract.h"
 
 #include <map>
 
@@ -413,6 +414,8 @@ extern "C" void pl_ocp_destroy(pl_ocp* o) {
     for (int k = 0; k < 5; ++k) hipEventDestroy(o->ev[k]);
     if (o->mpc_graph) hipGraphExecDestroy(o->mpc_graph);
     if (o->dl_host) hipHostFree(o->dl_host);
+    if (o->rt_dev) hipFree(o->rt_dev);
+    if (o->rt_host) hipHostFree(o->rt_host);
     hipStreamDestroy(o->h.stream);
   }
   delete o;
@@ -1266,6 +1269,89 @@ extern "C" int pl_mpc_download(pl_ocp* o, double* host_dst) {
                                 h->B, hipMemcpyDeviceToHost, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   memcpy(host_dst, o->dl_host, bytes);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Batched retract of the solved horizon (k_retract.hip, retract.h): what the reference's
+// retract_stacked_sol / compile_solution return per problem (ocp_whole_body_rnea.py:293-366)
+// plus the base rows of the equations of motion (run_mpc.py:211-233), for the whole batch.
+static int retract_args(const pl_ocp* o, int steps, int terminal) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  const int N = o->h.N;
+  if (steps < 1 || steps > N) { pl_set_error("retract: steps %d outside [1, %d]", steps, N); return -1; }
+  if (terminal != 0 && terminal != 1) { pl_set_error("retract: terminal must be 0 or 1, got %d", terminal); return -1; }
+  if (terminal && steps != N) { pl_set_error("retract: the terminal row needs steps == N (%d), got %d", N, steps); return -1; }
+  if (PL_IS_CV(o->h.oc.dyn) && N < 2) { pl_set_error("retract: centroidal_vel needs N >= 2"); return -1; }
+  return 0;
+}
+
+extern "C" int pl_ocp_retract_sizes(const pl_ocp* o, int steps, int terminal, long long* out) {
+  if (retract_args(o, steps, terminal)) return -1;
+  if (!out) { pl_set_error("null argument"); return -1; }
+  const pl::RetractLayout L = pl::retract_layout(o->h.oc, o->h.B, steps, terminal);
+  for (int k = 0; k < PL_RETRACT_FIELDS; ++k) {
+    out[3 * k] = L.width[k];
+    out[3 * k + 1] = L.rows[k];
+    out[3 * k + 2] = L.off[k];
+  }
+  out[3 * PL_RETRACT_FIELDS] = L.total;
+  return 0;
+}
+
+// the packed result into the handle's device buffer (grown on demand), on the handle's stream
+static int retract_enqueue(pl_ocp* o, int steps, int terminal, const pl::RetractLayout& L) {
+  const size_t need = (size_t)L.total;
+  if (o->rt_cap < need) {
+    PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
+    if (o->rt_dev) hipFree(o->rt_dev);
+    o->rt_dev = nullptr;
+    o->rt_cap = 0;
+    PL_CHECK_HIP(hipMalloc(&o->rt_dev, need * sizeof(double)));
+    o->rt_cap = need;
+  }
+  launch_retract(&o->h, steps, terminal, o->rt_dev);
+  PL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pl_ocp_retract_device(pl_ocp* o, int steps, int terminal, void* device_dst) {
+  if (retract_args(o, steps, terminal)) return -1;
+  REQUIRE_DEVICE(o);
+  if (!device_dst) { pl_set_error("null argument"); return -1; }
+  launch_retract(&o->h, steps, terminal, (double*)device_dst);
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
+  return 0;
+}
+
+extern "C" int pl_ocp_retract(pl_ocp* o, int steps, int terminal, double* q, double* v, double* a, double* forces,
+                              double* tau, double* eom_base) {
+  if (retract_args(o, steps, terminal)) return -1;
+  REQUIRE_DEVICE(o);
+  const pl::RetractLayout L = pl::retract_layout(o->h.oc, o->h.B, steps, terminal);
+  if (retract_enqueue(o, steps, terminal, L)) return -2;
+  const size_t bytes = (size_t)L.total * sizeof(double);
+  if (o->rt_host_bytes < bytes) {
+    if (o->rt_host) hipHostFree(o->rt_host);
+    o->rt_host = nullptr;
+    o->rt_host_bytes = 0;
+    PL_CHECK_HIP(hipHostMalloc(&o->rt_host, bytes, hipHostMallocDefault));
+    o->rt_host_bytes = bytes;
+  }
+  // only the wanted fields cross the bus (each is one contiguous range of the packed buffer)
+  double* dst[PL_RETRACT_FIELDS] = {q, v, a, forces, tau, eom_base};
+  double* stage = (double*)o->rt_host;
+  for (int k = 0; k < PL_RETRACT_FIELDS; ++k) {
+    const size_t len = (size_t)o->h.B * L.rows[k] * L.width[k];
+    if (dst[k] && len)
+      PL_CHECK_HIP(hipMemcpyAsync(stage + L.off[k], o->rt_dev + L.off[k], len * 8, hipMemcpyDeviceToHost, o->h.stream));
+  }
+  PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
+  for (int k = 0; k < PL_RETRACT_FIELDS; ++k) {
+    const size_t len = (size_t)o->h.B * L.rows[k] * L.width[k];
+    if (dst[k] && len) memcpy(dst[k], stage + L.off[k], len * 8);
+  }
   return 0;
 }
 

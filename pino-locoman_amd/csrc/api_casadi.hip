@@ -1,5 +1,6 @@
 // CasADi external-function ABI over the batched OCP (see the section comment below).
 #include "api_internal.h"
+#include "retract.h"
 
 // ---------------------------------------------------------------------------
 // CasADi external-function ABI.  The reference builds
@@ -348,71 +349,24 @@ extern "C" int retract_solution(const double** arg, double** res, casadi_int*, d
   const pl_ocp* o = g_cas.o;
   const PlModel& M = o->h.model;
   const PlOcpConst& O = o->h.oc;
-  const int S = g_cas.steps, nq = M.nq, nv = M.nv, nj = O.nj;
-  int na, nf, nt;
-  cas_u_split(o, na, nf, nt);
+  const int S = g_cas.steps;
   const int ntau = (int)g_cas.sp_tau[1];
-  const bool cv = PL_IS_CV(O.dyn);
-  std::vector<double> xs(O.nx), a(nv), tau(nv), vfull(nv), vnext(nv);
-  PlFrameRef F0;
-  memset(&F0, 0, sizeof(F0));
   const double* p = o->h_params.data();
-  if (cv && !(p[O.P.dt_min] > 0.0 && p[O.P.dt_max] > 0.0)) {
+  if (PL_IS_CV(O.dyn) && !(p[O.P.dt_min] > 0.0 && p[O.P.dt_max] > 0.0)) {
     pl_set_error("retract_solution: the bound centroidal_vel OCP has no step sizes (pl_ocp_set_params)");
     return 1;
   }
   for (int i = 0; i < S; ++i) {
-    const PlNode& nd = o->nodes[i];
-    const double* dx = arg[0] + nd.x_off;
-    const double* u = dx + o->h.ndx;
-    pl::dyn_eval(M, O, F0, cv ? PL_FN_INTEGRATE_CV : PL_FN_INTEGRATE_WB, 0, arg[1], dx, nullptr, nullptr, xs.data());
-    const double* q = cv ? xs.data() + 6 : xs.data();
-    const double* v = cv ? u : xs.data() + nq;
-    const double* f = u + (O.dyn == PL_DYN_ABA ? nj : na);
-    if (O.dyn == PL_DYN_CVNB) {  // v = [base_vel_dynamics(h, q, v_j), v_j] (ocp_centroidal_vel.py:228-235)
-      pl::dyn_eval(M, O, F0, PL_FN_BASE_VEL_CV, 0, xs.data(), q, u, nullptr, vfull.data());
-      for (int k = 0; k < nj; ++k) vfull[6 + k] = u[k];
-      v = vfull.data();
-    }
-    switch (O.dyn) {
-      case PL_DYN_ABA:
-        pl::dyn_eval(M, O, F0, PL_FN_ABA, 0, q, v, u, f, a.data());
-        break;
-      case PL_DYN_CV:
-      case PL_DYN_CVNB: {
-        const double dt = pl::node_dt(O, p, i);
-        const double* un = arg[0] + o->nodes[i + 1].x_off + o->h.ndx;
-        if (O.dyn == PL_DYN_CVNB) {  // v_next from this node's h, q (ocp_centroidal_vel.py:240-246)
-          pl::dyn_eval(M, O, F0, PL_FN_BASE_VEL_CV, 0, xs.data(), q, un, nullptr, vnext.data());
-          for (int k = 0; k < nj; ++k) vnext[6 + k] = un[k];
-          un = vnext.data();
-        }
-        for (int k = 0; k < nv; ++k) a[k] = (un[k] - v[k]) / dt;
-        pl::dyn_eval(M, O, F0, PL_FN_BASE_ACC_CV, 0, q, v, a.data() + 6, f, a.data());
-      } break;
-      case PL_DYN_ACCNB:  // a = [base_acc_dynamics(q, v, a_j, f), a_j] (ocp_whole_body_acc.py:124-135)
-        for (int k = 0; k < nj; ++k) a[6 + k] = u[k];
-        pl::dyn_eval(M, O, F0, PL_FN_BASE_ACC_WB, 0, q, v, u, f, a.data());
-        break;
-      default:
-        for (int k = 0; k < nv; ++k) a[k] = u[k];
-    }
-    if (O.dyn == PL_DYN_ACC || O.dyn == PL_DYN_CA || O.dyn == PL_DYN_ACCNB || cv)
-      pl::dyn_eval(M, O, F0, PL_FN_RNEA, 0, q, v, a.data(), f, tau.data());
     // CasADi dense matrices are column-major: element (row i, col k) at k * S + i
-    if (res[0]) for (int k = 0; k < nq; ++k) res[0][k * S + i] = q[k];
-    if (res[1]) for (int k = 0; k < nv; ++k) res[1][k * S + i] = v[k];
-    if (res[2] && O.dyn != PL_DYN_RNEAFD) for (int k = 0; k < nv; ++k) res[2][k * S + i] = a[k];
-    if (res[3]) for (int k = 0; k < nf; ++k) res[3][k * S + i] = f[k];
-    if (res[4]) {
-      for (int k = 0; k < ntau; ++k) {
-        double t;
-        if (PL_IS_RNEA(O.dyn)) t = u[na + nf + k];
-        else if (O.dyn == PL_DYN_ABA) t = u[k];
-        else t = tau[6 + k];
-        res[4][k * S + i] = t;
-      }
-    }
+    pl::RetractOut out;
+    out.q = res[0] ? res[0] + i : nullptr;
+    out.v = res[1] ? res[1] + i : nullptr;
+    out.a = res[2] ? res[2] + i : nullptr;
+    out.f = res[3] ? res[3] + i : nullptr;
+    out.tau = res[4] && ntau > 0 ? res[4] + i : nullptr;  // rnea past tau_nodes: no tau column here
+    out.eom = nullptr;
+    out.stride = S;
+    pl::retract_node(M, O, O.dyn, o->nodes.data(), o->h.N, p, arg[0], arg[1], i, out);
   }
   return 0;
 }

@@ -44,6 +44,12 @@ struct pl_ocp {
   long long mpc_replays = 0;           // graph launches (pl_mpc_graph_info)
   void* dl_host = nullptr;             // pinned staging of pl_mpc_download
   size_t dl_bytes = 0;
+  // pl_ocp_retract: the packed device result and its pinned staging, allocated on first use
+  // (here, not in `h`: the bytes of `h` are the MPC graph key)
+  double* rt_dev = nullptr;
+  size_t rt_cap = 0;                   // doubles
+  void* rt_host = nullptr;
+  size_t rt_host_bytes = 0;
 };
 
 template <class T>

@@ -372,6 +372,7 @@ void launch_unscale(PlOcpHandle* h);
 void launch_line_search(PlOcpHandle* h);
 void launch_mpc_prepare(PlOcpHandle* h, int k);
 void launch_mpc_finish(PlOcpHandle* h);
+void launch_retract(PlOcpHandle* h, int steps, int terminal, double* out);  // k_retract.hip
 void launch_reset_info(PlOcpHandle* h);
 void launch_reset_iterates(PlOcpHandle* h);
 void launch_reset_prof(PlOcpHandle* h);

@@ -102,6 +102,9 @@ EXPORTS = {
     "pl_mpc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "pl_mpc_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pl_mpc_download": (C.c_int, [C.c_void_p, _dp]),
+    "pl_ocp_retract_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "pl_ocp_retract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pl_ocp_retract_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pl_ocp_profile_read_hess": (C.c_int, [C.c_void_p, _dp]),
     "pl_mpc_graph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "pl_mpc_set_ip_lam": (C.c_int, [C.c_void_p, C.c_int]),

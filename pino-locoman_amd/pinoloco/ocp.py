@@ -419,6 +419,40 @@ class BatchedOCP:
         _lib.check(_lib.lib().pl_mpc_download(self.h, _lib.dptr(out)))
         return out
 
+    # ---------------------------------------------------------------- retract
+    RETRACT_FIELDS = ("q", "v", "a", "forces", "tau", "eom_base")
+
+    def retract_sizes(self, steps=None, terminal=False):
+        """Layout of the batched retract: per field of RETRACT_FIELDS its ``width``, ``rows`` and
+        ``offset`` (doubles) in the packed, field-major result ([batch][rows][width] each), and
+        ``total``, the doubles of the whole batch.  steps defaults to every node.  Needs no device."""
+        steps = self.layout.N if steps is None else int(steps)
+        out = (C.c_longlong * 19)()
+        _lib.check(_lib.lib().pl_ocp_retract_sizes(self.h, steps, int(bool(terminal)), out))
+        sz = {f: {"width": int(out[3 * k]), "rows": int(out[3 * k + 1]), "offset": int(out[3 * k + 2])}
+              for k, f in enumerate(self.RETRACT_FIELDS)}
+        sz["total"] = int(out[18])
+        return sz
+
+    def retract(self, steps=None, terminal=False):
+        """The current iterate of every problem retracted on the device (retract_stacked_sol,
+        ocp_whole_body_rnea.py:293-324 and its siblings; the torques and base residual of
+        run_mpc.py:186-241): a dict of [batch][rows][width] arrays q, v, a, forces, tau and
+        eom_base, the base rows of RNEA(q, v, a, forces).  terminal (needs steps == N) adds node
+        N's row to q and, except for centroidal_vel, to v.  Valid after solve() and mpc_step()."""
+        steps = self.layout.N if steps is None else int(steps)
+        sz = self.retract_sizes(steps, terminal)
+        out = {f: np.zeros((self.batch, sz[f]["rows"], sz[f]["width"])) for f in self.RETRACT_FIELDS}
+        _lib.check(_lib.lib().pl_ocp_retract(self.h, steps, int(bool(terminal)),
+                                             *[_lib.dptr(out[f]) for f in self.RETRACT_FIELDS]))
+        return out
+
+    def retract_device(self, ptr, steps=None, terminal=False):
+        """The packed result (retract_sizes) into a caller-owned device buffer of ``total``
+        doubles, e.g. a torch tensor's data_ptr(); returns after the kernel has finished."""
+        steps = self.layout.N if steps is None else int(steps)
+        _lib.check(_lib.lib().pl_ocp_retract_device(self.h, steps, int(bool(terminal)), C.c_void_p(ptr)))
+
     def mpc_set_ip_lam(self, carry):
         """Interior-point MPC loop: carry=False (default) the reference's default driver
         (compile_solver=True: primal warm start, cold multipliers, run_mpc.py:34-37, 50-111);
