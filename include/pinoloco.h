@@ -363,6 +363,17 @@ int pl_ocp_get_admm_kernel(const pl_ocp* o);
  * ceil((N + 1) / 8) while the batch's workgroups fit one per CU, else fewer (1 under
  * PL_PATH_RC_ONE_GROUP). */
 int pl_ocp_get_admm_groups(const pl_ocp* o);
+/* Small operands of the PL_ADMM_SWEEP kernel.  PL_ADMM_OPERANDS_FUSED (default): a step issues
+ * only the loads it consumes, and rho comes from the row bounds the step already holds where
+ * the OSQP path wrote it by its rule.  PL_ADMM_OPERANDS_SPLIT: the earlier path (every array on its own, every prefetch issued),
+ * kept as the regression reference.  Results are bit-identical; the other kernels ignore it.
+ * pl_ocp_get_admm_rho_from_bounds: 1 when a fused sweep launched now would compute rho from
+ * the bounds, 0 when it would stream it (after an interior-point solve, or in SPLIT mode). */
+#define PL_ADMM_OPERANDS_SPLIT 0
+#define PL_ADMM_OPERANDS_FUSED 1
+int pl_ocp_set_admm_operands(pl_ocp* o, int mode);
+int pl_ocp_get_admm_operands(const pl_ocp* o);
+int pl_ocp_get_admm_rho_from_bounds(const pl_ocp* o);
 
 /* Timing of the dominant kernel (ADMM sweeps) with HIP events on the handle's
  * stream: pl_ocp_profile(o, 1) clears and starts, pl_ocp_profile_read returns

@@ -256,6 +256,8 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   h.debug_paths = d->debug_paths;
   h.admm_waves = 1;
   h.admm_rc = 0;
+  h.admm_operands = PL_ADMM_OPERANDS_FUSED;  // pl_ocp_set_admm_operands: _SPLIT is the earlier path
+  h.admm_rho_rule = 0;                       // nothing has written d.rho yet
   h.rc_waves = 8;
   h.ruiz_fused = !(h.debug_paths & PL_PATH_RUIZ_PER_PASS);
   h.ch_stride = rc_ch_stride(h.N, h.ndx, h.rc_waves);
@@ -578,6 +580,33 @@ extern "C" int pl_ocp_set_admm_kernel(pl_ocp* o, int kind) {
 extern "C" int pl_ocp_get_admm_kernel(const pl_ocp* o) {
   if (!o) { pl_set_error("null handle"); return -1; }
   return o->h.admm_rc ? PL_ADMM_CHAIN : (o->h.admm_waves == 2 ? PL_ADMM_SWEEP2 : PL_ADMM_SWEEP);
+}
+
+// How k_admm (the "sweep" kernel) reads the small operands of a step: PL_ADMM_OPERANDS_FUSED
+// (default: unconsumed prefetches skipped, rho from the bounds where k_qp_finish wrote it) or
+// PL_ADMM_OPERANDS_SPLIT (the earlier path, the regression reference).  Bit-identical results; the other ADMM kernels ignore it.
+extern "C" int pl_ocp_set_admm_operands(pl_ocp* o, int mode) {
+  REQUIRE_DEVICE(o);
+  if (mode != PL_ADMM_OPERANDS_SPLIT && mode != PL_ADMM_OPERANDS_FUSED) {
+    pl_set_error("ADMM operand mode %d unknown", mode);
+    return -1;
+  }
+  PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
+  o->h.admm_operands = mode;  // inside the MPC-graph key: the next pl_mpc_step captures again
+  return 0;
+}
+
+extern "C" int pl_ocp_get_admm_operands(const pl_ocp* o) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  return o->h.admm_operands;
+}
+
+// 1 when a fused sweep launched now would compute rho from the bounds (d.rho was last written
+// by k_qp_finish), 0 when it would stream d.rho (the interior point's weights) or the mode is
+// PL_ADMM_OPERANDS_SPLIT.
+extern "C" int pl_ocp_get_admm_rho_from_bounds(const pl_ocp* o) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  return o->h.admm_operands == PL_ADMM_OPERANDS_FUSED && o->h.admm_rho_rule ? 1 : 0;
 }
 
 extern "C" int pl_ocp_get_admm_groups(const pl_ocp* o) {
@@ -1491,6 +1520,10 @@ static int debug_rw(pl_ocp* o, const char* name, double* out, const double* in, 
       else PL_CHECK_HIP(hipMemcpyAsync(it.p, in, it.len * 8, hipMemcpyHostToDevice, h->stream));
       if (in && it.p == h->d.Araw) {  // the constant entries are rewritten by the next (eager) step
         h->jac_cheap_ok = 0;
+        o->mpc_key.clear();
+      }
+      if (in && it.p == h->d.rho) {  // no longer k_qp_finish's values: the sweep streams them
+        h->admm_rho_rule = 0;
         o->mpc_key.clear();
       }
       PL_CHECK_HIP(hipStreamSynchronize(h->stream));

@@ -78,10 +78,31 @@ struct AdmmLds {
 
 }  // namespace
 
-template <int PPW, int ASR, bool TIMING, bool NT>
+// OPS selects how the small operands of a step are read (pl_ocp_set_admm_operands):
+//   OPS_SPLIT  the earlier path, kept as the regression reference: z, y, rho, l, u and x, q from
+//              their own arrays, every prefetch issued in every step (the ones a step does not
+//              consume clamped to one element);
+//   OPS_FUSED  a prefetch nothing consumes is not issued (a wave-uniform branch on the next
+//              step's kind); rho is streamed (the interior point's per-row weights);
+//   OPS_FUSED_RHO  as OPS_FUSED, and rho is not read at all: it is one of three values by
+//              k_qp_finish's rule on the l, u the step already holds (rho0 = settings.rho).
+// The arithmetic is the same in all three: a problem's results are bit-identical.  (Pair-
+// interleaved z|y, l|u, x|q copies read with 16-byte loads were measured too and made the
+// launch 6-11 % slower: profiles/r07)
+enum { OPS_SPLIT = 0, OPS_FUSED = 1, OPS_FUSED_RHO = 2 };
+
+__device__ __forceinline__ double uniform_f64(double x) {  // a wave-uniform double into scalar registers
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+
+template <int PPW, int ASR, bool TIMING, bool NT, int OPS>
 __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int n, int m, int nnz, int ndx,
                                                       int S_stride, int cpl_stride, AdmmLds lm, int niter, int check,
-                                                      int fwd_asb, double sigma, double alpha) {
+                                                      int fwd_asb, double sigma, double alpha, double rho0) {
+  constexpr bool kFused = OPS != OPS_SPLIT;
+  constexpr bool kRule = OPS == OPS_FUSED_RHO;
   extern __shared__ double lds[];
   {  // every node program, shared by the waves of the workgroup
     const uint4* src = reinterpret_cast<const uint4*>(d.aprog);
@@ -134,6 +155,9 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
   double* bt = d.bt + (size_t)b * n;
   double* dxs = d.dxs + (size_t)b * n;
   double* dys = d.dys + (size_t)b * m;
+  // kRule: the three rho classes of k_qp_finish and their reciprocals, wave-uniform
+  const double rho_in = uniform_f64(rho0), rho_eq = uniform_f64(PL_RHO_EQ_OVER_INEQ * rho0);
+  const double irho_in = uniform_f64(1.0 / rho_in), irho_eq = uniform_f64(1.0 / rho_eq);
   // NT: the batch's factor far exceeds the 256 MB Infinity Cache (admm_config), so the streams
   // (factor blocks, A, the row / column operands) are non-temporal loads; below it the sweeps'
   // re-reads partly hit the cache and plain loads are kept (Go2 centroidal_vel at B = 1024:
@@ -160,6 +184,14 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
   // at BWD 1 -> T0 -> FWD 1 step q+1 is forward and consumes no LR / LC.  (With N = 1,
   // TN -> T0 -> TN would read x of node N before the first TN's store of it.)  The other
   // operands of step q+1 (E, las) are issued after the stores, in order.
+  // On the fused path a prefetch that step q+1 does not consume is skipped, not clamped: LR is
+  // loaded exactly when step q+1 is a backward kind, LC when it is backward or TN, las when the
+  // step stages A (backward, or forward with fwd_asb) -- the conditions under which the step
+  // reads them, each a function of the readfirstlane-uniform kind1 (and fwd_asb) alone.  So
+  // every consumed operand is still loaded one step ahead under the argument above, and a
+  // skipped one leaves the registers of the step before, or none yet (never read).
+  // The wait stays the single vmcnt(0) at the step start, which counts nothing: a step that
+  // issued fewer loads waits for fewer.
   Sbuf SR;  // factor slots of the current block; refilled with the next block's as they are consumed
   Early E, En;  // current / next step (the copy at the start of a step is its only vmcnt wait)
   double las[ASR];
@@ -169,7 +201,8 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
   double2 r0v = make_double2(0.0, 0.0);  // rhs_0 of the backward-0 half of T0 (columns lane, lane + 64)
   bool fix1 = false;
 
-  // ---------------- loads (unconditional and clamped: exact vmcnt accounting)
+  // ---------------- loads (OPS_SPLIT: unconditional and clamped, as when the waits were counted;
+  // fused: a group no step consumes is skipped under a wave-uniform condition)
   auto load_S = [&](int i, int kbase, Sbuf& R) __attribute__((always_inline)) {
     const int K = an[i].nunit;
     const double2* p = reinterpret_cast<const double2*>(Sg + an[i].s_off);
@@ -188,6 +221,8 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
     {  // coupling A values through registers, contiguous per node (d.Acpl, k_acpl)
       const double* Ac = Acp + (size_t)g * PL_ACPL;
       const int o1 = fw ? lane * CWM : 0, o2 = fw ? 64 * CWM + lane * XCM : 0;  // backward: unused, one line
+      // (not skipped on the fused path: a branch around these three loads took the headline
+      // instantiation from 198 to 200 AGPRs, profiles/r07/resources.txt)
 #pragma unroll
       for (int k = 0; k < CWM; ++k) E.acw[k] = gld(Ac, o1 + k);
 #pragma unroll
@@ -206,18 +241,21 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
     const bool bw = bwd_kind(kind1) || fa;
     const int ia = fa ? i1 - 1 : i1;
     const int eo = an[ia].ent_off, ne = an[ia].nent;
+    if (!kFused || bw) {  // fused: a step that stages nothing loads nothing
 #pragma unroll
-    for (int k = 0; k < ASR; ++k) las[k] = gldx<NT>(As, eo + (bw ? min(lane + 64 * k, ne - 1) : 0));
+      for (int k = 0; k < ASR; ++k) las[k] = gldx<NT>(As, eo + (bw ? min(lane + 64 * k, ne - 1) : 0));
+    }
   };
   auto prefetch_LR = [&](int kind1, int i1, LateR& LR) __attribute__((always_inline)) {
     const bool bw = bwd_kind(kind1);
     const int ro = an[i1].row_off, nr = an[i1].nrow;
+    if (kFused && !bw) return;  // only a backward step reads its rows
 #pragma unroll
     for (int mm = 0; mm < MR; ++mm) {
       const int r = ro + (bw ? min(lane + 64 * mm, max(nr - 1, 0)) : 0);
       LR.z[mm] = gldx<NT>(za, r);
       LR.y[mm] = gldx<NT>(ya, r);
-      LR.rho[mm] = gldx<NT>(rho, r);
+      if constexpr (!kRule) LR.rho[mm] = gldx<NT>(rho, r);
       LR.l[mm] = gldx<NT>(ls, r);
       LR.u[mm] = gldx<NT>(us, r);
     }
@@ -225,6 +263,7 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
   auto prefetch_LC = [&](int kind1, int i1, LateC& LC) __attribute__((always_inline)) {
     const bool need = bwd_kind(kind1) || kind1 == KTN;
     const int xo = an[i1].x_off, nw1 = an[i1].nw;
+    if (kFused && !need) return;
 #pragma unroll
     for (int mm = 0; mm < MV; ++mm) {
       const int j = xo + (need ? min(lane + 64 * mm, nw1 - 1) : 0);
@@ -647,12 +686,22 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
               const int k0 = P[rcp + r], k1 = P[rcp + r + 1];
               const double zt = lds_sum<4>(part, k0, k1, 1, zslot);
 #endif
+              double rr, ri;  // rho of the row and 1 / rho
+              if constexpr (kRule) {  // k_qp_finish's rule on the stored l, u (same comparisons, same values)
+                const bool unb = LR.l[mm] < -PL_OSQP_INFTY * PL_MIN_SCALING && LR.u[mm] > PL_OSQP_INFTY * PL_MIN_SCALING;
+                const bool eq = LR.u[mm] - LR.l[mm] < PL_RHO_TOL;
+                rr = unb ? PL_RHO_MIN : (eq ? rho_eq : rho_in);
+                ri = unb ? 1.0 / PL_RHO_MIN : (eq ? irho_eq : irho_in);
+              } else {
+                rr = LR.rho[mm];
+                ri = 1.0 / LR.rho[mm];
+              }
               const double zrel = alpha * zt + (1.0 - alpha) * LR.z[mm];
-              double zn = zrel + (1.0 / LR.rho[mm]) * LR.y[mm];
+              double zn = zrel + ri * LR.y[mm];
               zn = fmin(fmax(zn, LR.l[mm]), LR.u[mm]);
-              const double dy = LR.rho[mm] * (zrel - zn);
+              const double dy = rr * (zrel - zn);
               const double yn = LR.y[mm] + dy;
-              trow[r] = LR.rho[mm] * zn - yn;
+              trow[r] = rr * zn - yn;
               kz[mm] = zn;
               ky[mm] = yn;
               kd[mm] = dy;
@@ -890,17 +939,27 @@ AdmmCfg admm_config(const PlOcpHandle* h) {
   return c;
 }
 
-template <int PPW, int ASR, bool TIMING, bool NT>
-void launch_admm_nt(PlOcpHandle* h, int niter, int check, const AdmmCfg& c) {
+template <int PPW, int ASR, bool TIMING, bool NT, int OPS>
+void launch_admm_ops(PlOcpHandle* h, int niter, int check, const AdmmCfg& c) {
   static bool attr = false;
   if (!attr) {
-    hipFuncSetAttribute((const void*)k_admm<PPW, ASR, TIMING, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)k_admm<PPW, ASR, TIMING, NT, OPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        160 * 1024);
     attr = true;
   }
   const int grid = (h->B + PPW - 1) / PPW;
-  hipLaunchKernelGGL((k_admm<PPW, ASR, TIMING, NT>), dim3(grid), dim3(64 * PPW), c.lds, h->stream, h->d, h->B, h->N,
-                     h->n, h->m, h->nnz, h->ndx, h->S_stride, std::max(h->ncpl_max, 1), c.lm, niter, check,
-                     h->admm_fwd_asb, h->set.sigma, h->set.alpha);
+  hipLaunchKernelGGL((k_admm<PPW, ASR, TIMING, NT, OPS>), dim3(grid), dim3(64 * PPW), c.lds, h->stream, h->d, h->B,
+                     h->N, h->n, h->m, h->nnz, h->ndx, h->S_stride, std::max(h->ncpl_max, 1), c.lm, niter, check,
+                     h->admm_fwd_asb, h->set.sigma, h->set.alpha, h->set.rho);
+}
+
+template <int PPW, int ASR, bool TIMING, bool NT>
+void launch_admm_nt(PlOcpHandle* h, int niter, int check, const AdmmCfg& c) {
+  // rho from the bounds only while d.rho holds what k_qp_finish's rule wrote (the interior
+  // point's k_ip_kkt writes per-row weights that follow no rule: streamed)
+  if (h->admm_operands != PL_ADMM_OPERANDS_FUSED) launch_admm_ops<PPW, ASR, TIMING, NT, OPS_SPLIT>(h, niter, check, c);
+  else if (h->admm_rho_rule) launch_admm_ops<PPW, ASR, TIMING, NT, OPS_FUSED_RHO>(h, niter, check, c);
+  else launch_admm_ops<PPW, ASR, TIMING, NT, OPS_FUSED>(h, niter, check, c);
 }
 
 template <int PPW, int ASR, bool TIMING = false>

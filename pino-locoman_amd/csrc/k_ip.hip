@@ -877,6 +877,7 @@ void enqueue_ip(PlOcpHandle* h) {
     launch_eval_jac(h);
     hipLaunchKernelGGL(k_ip_kkt, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
                        std::max(h->ncpl_max, 1), k, st);
+    h->admm_rho_rule = 0;  // d.rho = W, per-row weights: the sweep streams it
     if (k == st.max_iter) break;
     if (h->ip_hess == PL_IP_HESS_EXACT) launch_lag_hess(h);
     ip_factor(h);
@@ -908,6 +909,7 @@ void enqueue_ip_direction(PlOcpHandle* h) {
   launch_eval_jac(h);
   hipLaunchKernelGGL(k_ip_kkt, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
                      std::max(h->ncpl_max, 1), -1, st);
+  h->admm_rho_rule = 0;
   if (h->ip_hess == PL_IP_HESS_EXACT) launch_lag_hess(h);
   ip_factor(h);
   launch_admm_init(h);

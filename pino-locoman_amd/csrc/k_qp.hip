@@ -23,12 +23,8 @@
 
 #include "state.h"
 
-#define PL_OSQP_INFTY 1e30
-#define PL_MIN_SCALING 1e-4
+// PL_OSQP_INFTY, PL_MIN_SCALING and the PL_RHO_* constants: state.h (k_admm shares them)
 #define PL_MAX_SCALING 1e4
-#define PL_RHO_MIN 1e-6
-#define PL_RHO_TOL 1e-4
-#define PL_RHO_EQ_OVER_INEQ 1e3
 #define PL_DIV_TOL 1e-30
 
 enum {
@@ -430,6 +426,7 @@ __global__ __launch_bounds__(256) void k_qp_finish(PlDev d, int N, int n, int m,
 
 void launch_qp_setup(PlOcpHandle* h) {
   const dim3 nodes_grid(h->B * (h->N + 1));
+  h->admm_rho_rule = 1;  // k_qp_finish (below, on both paths) writes d.rho by its rule on ls, us
   if (h->ruiz_fused && ruiz_fused_supported(h)) {
     static bool fattr = false;
     if (!fattr) {

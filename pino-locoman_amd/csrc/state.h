@@ -77,6 +77,17 @@ struct PlNode {
 #define PL_ADMM_ASR_MAX 32  // A values per lane staged through registers (entries past 64 x ASR: global)
 #define PL_ACPL (64 * (PL_ADMM_CWM + PL_ADMM_XCM))  // coupling A values per node (d.Acpl)
 #define PL_RC_SYNC 32       // k_admm_rc hand-off words per problem (one 128-byte line)
+#ifndef PL_ADMM_OPERANDS_SPLIT  // include/pinoloco.h (pl_ocp_set_admm_operands)
+#define PL_ADMM_OPERANDS_SPLIT 0
+#define PL_ADMM_OPERANDS_FUSED 1
+#endif
+// OSQP 0.6 constants of the row bounds and rho (k_qp_finish writes d.rho by this rule; k_admm
+// recomputes it from the stored bounds on the fused operand path)
+#define PL_OSQP_INFTY 1e30
+#define PL_MIN_SCALING 1e-4
+#define PL_RHO_MIN 1e-6
+#define PL_RHO_TOL 1e-4
+#define PL_RHO_EQ_OVER_INEQ 1e3
 struct PlAdmmNode {
   int nw, nrow, ncol, ncpl, nent, nunit, ntile, ntl;  // nunit = K slots, ntile = T, ntl = tiles
   unsigned kmagic;  // ceil(2^32 / K): t / K == umulhi(t, kmagic) for the tile counts used
@@ -211,7 +222,7 @@ struct PlDev {
   double* ya;
   double* rhs;
   double* bt;
-  double* dxs;       // delta x (check iterations)
+  double* dxs;      // delta x (check iterations)
   double* dys;       // delta y
   double* aty;       // A^T y scratch (check iterations)
   double* step;      // unscaled QP step dx
@@ -279,6 +290,7 @@ struct PlOcpHandle {
   int admm_fwd_asb;                 // coupling rows too dense for registers: forward steps stage A in LDS
   int sqp_iters;                    // SQP iterations per solve (reference: 1, ocp.py:382-383)
   int admm_waves;                   // ADMM sweep kernel: 2 = k_admm2 (two waves per problem), 1 = k_admm
+  int admm_operands;                // k_admm's small operands: PL_ADMM_OPERANDS_FUSED (default) or _SPLIT
   int ruiz_fused;                   // 1: all equilibration passes in k_ruiz_fused (PL_PATH_RUIZ_PER_PASS: per-pass kernels)
   unsigned debug_paths;             // pl_ocp_desc.debug_paths (PL_PATH_*), 0 in production
   int admm_rc;                      // 1: reduced-chain ADMM (k_admm_rc.hip) instead of the sweeps
@@ -333,6 +345,10 @@ struct PlOcpHandle {
   // outside the MPC-graph key (api.hip kMpcKeyBytes): set by the first Jacobian evaluation,
   // which runs eagerly; a debug write of Araw clears it and the key
   int jac_cheap_ok;                 // the cheap columns' constant entries are in d.Araw
+  // also outside the key: who wrote d.rho last, set while the writer is enqueued (the same
+  // sequence at capture and in eager runs).  1: k_qp_finish, by its rule on ls, us -- the fused
+  // k_admm recomputes rho from them; 0: k_ip_kkt (per-row weights) or a debug write -- streamed
+  int admm_rho_rule;
   hipEvent_t prof_ev[64][2];
   int prof_n;
   double prof_admm_ms;

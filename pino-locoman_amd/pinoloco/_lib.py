@@ -85,6 +85,9 @@ EXPORTS = {
     "pl_ocp_set_admm_kernel": (C.c_int, [C.c_void_p, C.c_int]),
     "pl_ocp_get_admm_kernel": (C.c_int, [C.c_void_p]),
     "pl_ocp_get_admm_groups": (C.c_int, [C.c_void_p]),
+    "pl_ocp_set_admm_operands": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl_ocp_get_admm_operands": (C.c_int, [C.c_void_p]),
+    "pl_ocp_get_admm_rho_from_bounds": (C.c_int, [C.c_void_p]),
     "pl_ocp_set_ip_settings": (C.c_int, [C.c_void_p, C.POINTER(IpSettings)]),
     "pl_ocp_ip_stats": (C.c_int, [C.c_void_p, C.POINTER(IpStats)]),
     "pl_ocp_get_lam": (C.c_int, [C.c_void_p, _dp]),

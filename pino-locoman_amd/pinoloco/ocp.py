@@ -285,6 +285,25 @@ class BatchedOCP:
         over several; the sweep kernels use 1)."""
         return _lib.lib().pl_ocp_get_admm_groups(self.h)
 
+    ADMM_OPERANDS = {"split": 0, "fused": 1}
+
+    def set_admm_operands(self, mode):
+        """How the "sweep" ADMM kernel reads a step's small operands: "fused" (default: only
+        the loads a step consumes, rho from the row bounds on the OSQP path) or "split" (the earlier path, the regression reference).  Bit-identical
+        results; the other kernels ignore it."""
+        if mode not in self.ADMM_OPERANDS:
+            raise ValueError(f"ADMM operand mode {mode} unknown (choose from {sorted(self.ADMM_OPERANDS)})")
+        _lib.check(_lib.lib().pl_ocp_set_admm_operands(self.h, self.ADMM_OPERANDS[mode]))
+
+    def admm_operands(self):
+        code = _lib.lib().pl_ocp_get_admm_operands(self.h)
+        return {v: k for k, v in self.ADMM_OPERANDS.items()}[code]
+
+    def admm_rho_from_bounds(self):
+        """True when a fused sweep launched now would compute rho from the bounds (the OSQP
+        path wrote it), False when it would stream it (interior-point weights, "split")."""
+        return bool(_lib.lib().pl_ocp_get_admm_rho_from_bounds(self.h))
+
     def set_solver(self, solver):
         """"osqp" (SQP + OSQP, ocp.py:265-313 / 375-422) or "fatrop" (the interior-point
         restatement of the Fatrop branch, ocp.py:248-263 / 360-373)."""
