@@ -249,6 +249,35 @@ int pl_mpc_setup(pl_ocp* o, const double* x_state, const double* t0);
  * graph captured on the second step with unchanged handle settings (bit-identical to
  * launching them; PL_MPC_GRAPH=0 at creation launches them one by one). */
 int pl_mpc_step(pl_ocp* o, int k);
+/* The plant of the loop: how the true state x_state moves from step k to k + 1.  The reference
+ * closes the loop on the optimiser's own prediction (run_mpc.py:142), which lets no problem
+ * deviate from its plan; its commented-out "add noise to x_init" (run_mpc.py:79-82) and its
+ * dt_min "used for simulation" (run_mpc.py:18) point at a disturbed, simulated plant.
+ * PL_PLANT_ABA, per problem, after the solve of step k:
+ *   tau_cmd, f_cmd = tau and forces of node 0 as pl_ocp_retract(steps = 1) returns them (u's tau
+ *     block where it exists, else the joint rows of RNEA at the believed state x_init);
+ *   (q, v) = x_state, h = dt_min / substeps (the problem's own dt_min parameter);
+ *   substeps times: a = ABA(q, v, [w_b; tau_cmd], f_cmd) (pinocchio::aba with f_ext as
+ *     dynamics_whole_body_torque.py:55-103 builds it, re-expressed at each substep's q),
+ *     q <- integrate(q, v h), v <- v + a h: explicit Euler with the old v, the OCP's own
+ *     discretisation (ocp_whole_body_rnea.py:155-158).
+ * There is no contact model: the forces are the commanded ones, world-aligned at the feet and,
+ * where the robot has one, the external-force frame.  Works on a handle without a device;
+ * substeps in [1, 16]; PL_PLANT_ABA needs x = [q, v]: every dynamics kind but centroidal_vel
+ * (x = [h, q], dynamics_centroidal_vel.py:12-26).  The OSQP step re-captures its graph once
+ * after a change; the interior-point step uses the plant alike. */
+#define PL_PLANT_NOMINAL 0   /* x_state <- integrate(x_state, DX[1]) (run_mpc.py:142), the default */
+#define PL_PLANT_ABA     1   /* forward dynamics under the commanded torques / forces, above */
+int pl_mpc_set_plant(pl_ocp* o, int mode, int substeps);
+int pl_mpc_get_plant(const pl_ocp* o, int* mode, int* substeps);
+/* Disturbances of the loop, copied into device buffers of the handle; they hold until the next
+ * call (a push lasts as many steps as the caller leaves it set) and never re-capture the graph
+ * by their values.  base_wrench [batch][6] or NULL (= none): w_b, the generalised force on
+ * v[0:6] of the free-flyer, linear then angular, in the base frame (the base rows of
+ * pinocchio::aba's tau); read by PL_PLANT_ABA only.  state_noise [batch][ndx] or NULL (= none):
+ * the MPC plans from the measured state x_init = state_integrate(x_state, noise)
+ * (run_mpc.py:79-82) while x_state stays the true state; under either plant. */
+int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, const double* state_noise);
 int pl_mpc_get_state(pl_ocp* o, double* x_state);
 /* Solver stats of the last MPC step's (last) SQP iteration, as pl_ocp_solve reports. */
 int pl_mpc_get_stats(pl_ocp* o, pl_stats* stats);

@@ -245,6 +245,9 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   h.set.check_termination = d->check_termination;
   h.set.warm_start = d->warm_start;
   h.sqp_iters = 1;
+  h.plant_mode = PL_PLANT_NOMINAL;  // pl_mpc_set_plant / pl_mpc_set_disturbance: the loop follows its own plan
+  h.plant_substeps = 1;
+  h.plant_noise_on = 0;
   h.solver = PL_SOLVER_OSQP;
   // Fatrop settings of the reference (ocp.py:254-262) + the restatement's constants
   // (oracle/ip_ref.py IP_SETTINGS)
@@ -386,6 +389,10 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   rc |= dalloc(o, &D.info, B);
   rc |= dalloc(o, &D.t0, B);
   rc |= dalloc(o, &D.xstate, B * (size_t)h.nx);
+  // the plant's disturbances (pl_mpc_set_disturbance), zeroed: allocated here so that their
+  // pointers, part of the MPC graph's launches, never change
+  rc |= dalloc(o, &D.plant_w, B * 6);
+  rc |= dalloc(o, &D.plant_noise, B * (size_t)h.ndx);
   D.dbg = nullptr;
   if (h.debug_paths & PL_PATH_ADMM_TIMING) rc |= dalloc(o, &D.dbg, B * 40);
   if (rc) { pl_ocp_destroy(o); return -2; }
@@ -1140,6 +1147,49 @@ extern "C" int pl_mpc_setup(pl_ocp* o, const double* x_state, const double* t0) 
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// The plant of the loop: what turns the solve of step k into the true state of step k + 1.
+// PL_PLANT_NOMINAL is the reference's own loop, the optimiser's prediction (run_mpc.py:142);
+// PL_PLANT_ABA steps the forward dynamics under the commanded torques and forces and a base
+// wrench (plant.h, k_plant.hip).  The settings are host state inside the MPC graph key; the
+// disturbance values are device data the launches read, so new values replay.
+extern "C" int pl_mpc_set_plant(pl_ocp* o, int mode, int substeps) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (mode != PL_PLANT_NOMINAL && mode != PL_PLANT_ABA) { pl_set_error("pl_mpc_set_plant: unknown mode %d", mode); return -1; }
+  if (substeps < 1 || substeps > 16) { pl_set_error("pl_mpc_set_plant: substeps %d outside [1, 16]", substeps); return -1; }
+  if (mode == PL_PLANT_ABA && PL_IS_CV(o->h.oc.dyn)) {
+    pl_set_error("pl_mpc_set_plant: PL_PLANT_ABA is defined on x = [q, v]; centroidal_vel has x = [h, q]");
+    return -1;
+  }
+  o->h.plant_mode = mode;
+  o->h.plant_substeps = substeps;
+  return 0;
+}
+
+extern "C" int pl_mpc_get_plant(const pl_ocp* o, int* mode, int* substeps) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (mode) *mode = o->h.plant_mode;
+  if (substeps) *substeps = o->h.plant_substeps;
+  return 0;
+}
+
+extern "C" int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, const double* state_noise) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  const size_t wb = (size_t)h->B * 6 * 8, nb = (size_t)h->B * h->ndx * 8;
+  if (base_wrench) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_w, base_wrench, wb, hipMemcpyHostToDevice, h->stream));
+  else PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, wb, h->stream));  // k_plant always reads it: zero = none
+  if (state_noise) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_noise, state_noise, nb, hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  h->plant_noise_on = state_noise ? 1 : 0;  // off: k_mpc_prepare's plain copy of x_state
+  return 0;
+}
+
+static void enqueue_mpc_plant(PlOcpHandle* h) {
+  if (h->plant_mode == PL_PLANT_ABA) launch_plant(h);
+  else launch_mpc_finish(h);
+}
+
 // The OSQP-SQP part of an MPC step (every launch after k_mpc_prepare) as one HIP graph.
 // The sequence is fixed by the handle's host state (sizes, settings, kernel choice,
 // device pointers): it is captured on the second step that sees the same bytes of `h`
@@ -1149,7 +1199,7 @@ extern "C" int pl_mpc_setup(pl_ocp* o, const double* x_state, const double* t0) 
 // is the eager sequence.  Profiling runs (per-launch events) and PL_MPC_GRAPH=0 stay eager.
 static void enqueue_mpc_sqp(pl_ocp* o) {
   for (int it = 0; it < o->h.sqp_iters; ++it) enqueue_solve(o, false);
-  launch_mpc_finish(&o->h);
+  enqueue_mpc_plant(&o->h);
 }
 
 // The key is the handle up to its profiling fields: every launcher takes its launch
@@ -1243,7 +1293,7 @@ extern "C" int pl_mpc_step(pl_ocp* o, int k) {
       // from cold multipliers
       h->ip_lam_warm = 0;
     }
-    launch_mpc_finish(&o->h);
+    enqueue_mpc_plant(&o->h);
   } else
     enqueue_mpc_sqp(o);
   PL_CHECK_HIP(hipGetLastError());

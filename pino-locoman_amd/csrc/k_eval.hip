@@ -410,13 +410,31 @@ void launch_line_search(PlOcpHandle* h) {
 // MPC step k, before the solve: parameters (x_init, gait schedule at
 // t0 + k dt_min) and warm start (forces <- f_des masked by the new schedule;
 // ocp_whole_body_rnea.py:207-235).  k == 0 keeps the initial guess.
+// noise (pl_mpc_set_disturbance, null: none): the MPC plans from the measured state
+// x_init = state_integrate(x_state, noise_b), the "add noise to x_init" of run_mpc.py:79-82;
+// x_state stays the true state.
 __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n, int np, int nx, int gait_type,
-                                                    double period, double swing_period) {
+                                                    double period, double swing_period, const double* noise) {
   const int b = blockIdx.x;
   const PlOcpConst& O = *d.oc;
   const PlModel& M = *d.model;
   double* p = d.p + (size_t)b * np;
-  for (int j = threadIdx.x; j < nx; j += blockDim.x) p[O.P.x_init + j] = d.xstate[(size_t)b * nx + j];
+  if (!noise) {
+    for (int j = threadIdx.x; j < nx; j += blockDim.x) p[O.P.x_init + j] = d.xstate[(size_t)b * nx + j];
+  } else if (threadIdx.x == 0) {
+    const double* xs = d.xstate + (size_t)b * nx;
+    const double* nb = noise + (size_t)b * O.ndx;
+    double* xi = p + O.P.x_init;
+    if (PL_IS_CV(O.dyn)) {  // x = [h, q] (dynamics_centroidal_vel.py:12-26)
+      VecIn<double> acc{nb + 6, nullptr, 0.0, -1};
+      for (int j = 0; j < 6; ++j) xi[j] = xs[j] + nb[j];
+      pl::integrate_q<double>(M, xs + 6, acc, xi + 6);
+    } else {
+      VecIn<double> acc{nb, nullptr, 0.0, -1};
+      pl::integrate_q<double>(M, xs, acc, xi);
+      for (int j = 0; j < O.nv; ++j) xi[O.nq + j] = xs[O.nq + j] + nb[O.nv + j];
+    }
+  }
   if (threadIdx.x == 0) {
     double t = d.t0[b] + k * p[O.P.dt_min];
     pl::gait_schedule(O, gait_type, period, swing_period, t, p, p + O.P.contact, p + O.P.swing);
@@ -459,7 +477,8 @@ __global__ void k_mpc_finish(PlDev d, int B, int n, int nx) {
 
 void launch_mpc_prepare(PlOcpHandle* h, int k) {
   hipLaunchKernelGGL(k_mpc_prepare, dim3(h->B), dim3(64), 0, h->stream, h->d, k, h->N, h->n, h->np, h->nx,
-                     h->gait_type, h->gait_period, h->swing_period);
+                     h->gait_type, h->gait_period, h->swing_period,
+                     h->plant_noise_on ? (const double*)h->d.plant_noise : nullptr);
 }
 
 void launch_mpc_finish(PlOcpHandle* h) {

@@ -833,9 +833,16 @@ template <class S> PL_HD void actinv_matrix(const S* R, const S* p, S* X) {
     }
 }
 
-template <class S, class InT, class InF>
+// The generalised force on the free-flyer's own coordinates v[0:6] (linear then angular, in the
+// base frame): the base rows of pinocchio::aba's tau.  The OCP's dynamics leave the base
+// unactuated (NoBaseWrench: u_root = -pA, as before); the MPC plant (plant.h) passes a push.
+struct NoBaseWrench {};
+template <class S> PL_HD S aba_root_force(const NoBaseWrench&, int, const S& pA) { return -pA; }
+template <class S, class InW> PL_HD S aba_root_force(const InW& w, int k, const S& pA) { return w[k] - pA; }
+
+template <class S, class InT, class InF, class InW = NoBaseWrench>
 PL_HD void aba_forward(const PlModel& M, const PlOcpConst& O, const S* q, const S* v, const InT& tau_j,
-                       const InF& forces, S* ddq) {
+                       const InF& forces, S* ddq, const InW& base_wrench = InW()) {
   const int nb = M.njoints;
   S lR[PL_MAXJ][9], lp[PL_MAXJ][3], oR[PL_MAXJ][9];
   S vv[PL_MAXJ][6], cc[PL_MAXJ][6], pA[PL_MAXJ][6], Ia[PL_MAXJ][36];
@@ -890,7 +897,7 @@ PL_HD void aba_forward(const PlModel& M, const PlOcpConst& O, const S* q, const 
   for (int j = nb - 1; j >= 1; --j) {
     const int par = M.parent[j];
     if (M.jtype[j] == PL_JT_FREEFLYER) {
-      for (int k = 0; k < 6; ++k) u_root[k] = -pA[j][k];  // base torque = 0
+      for (int k = 0; k < 6; ++k) u_root[k] = aba_root_force<S>(base_wrench, k, pA[j][k]);  // base torque = 0 or w
       continue;                                           // root: parent is universe
     }
     const double* ax = M.axis[j];

@@ -233,6 +233,8 @@ struct PlDev {
   // MPC (device loop)
   double* t0;        // per-problem gait time offset
   double* xstate;    // per-problem current state x_init (nx)
+  double* plant_w;   // [B][6] base wrench of the plant (pl_mpc_set_disturbance; zero rows: none), k_plant.hip
+  double* plant_noise;  // [B][ndx] state noise of the measured x_init (read while PlOcpHandle::plant_noise_on)
   double* dbg;       // optional kernel timing [B][16] (PL_ADMM_TIMING=1 at handle creation)
   // interior point [B][m] (allocated by pl_ocp_set_solver(o, PL_SOLVER_IP))
   double* ip_s;      // slacks of the inequality rows
@@ -337,6 +339,12 @@ struct PlOcpHandle {
   int gait_type;     // 0 trot, 1 walk, 2 stand
   double gait_period, swing_period;
   double f_des[PL_MAXNU];
+  // the plant of pl_mpc_step (pl_mpc_set_plant, pl_mpc_set_disturbance); here, inside the
+  // MPC-graph key, so a change of the captured launch re-captures; the disturbance values live
+  // in d.plant_w / d.plant_noise, whose pointers never change
+  int plant_mode;                   // PL_PLANT_NOMINAL (k_mpc_finish) or PL_PLANT_ABA (k_plant)
+  int plant_substeps;               // Euler substeps of dt_min, [1, 16]
+  int plant_noise_on;               // 1: k_mpc_prepare writes x_init = state_integrate(x_state, noise)
   PlDev d;
   // host copies of the structure
   int* h_nodes_raw;
@@ -388,6 +396,7 @@ void launch_unscale(PlOcpHandle* h);
 void launch_line_search(PlOcpHandle* h);
 void launch_mpc_prepare(PlOcpHandle* h, int k);
 void launch_mpc_finish(PlOcpHandle* h);
+void launch_plant(PlOcpHandle* h);  // k_plant.hip
 void launch_retract(PlOcpHandle* h, int steps, int terminal, double* out);  // k_retract.hip
 void launch_reset_info(PlOcpHandle* h);
 void launch_reset_iterates(PlOcpHandle* h);

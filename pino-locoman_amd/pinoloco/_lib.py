@@ -101,6 +101,9 @@ EXPORTS = {
     "pl_ocp_get_step": (C.c_int, [C.c_void_p, _dp]),
     "pl_mpc_setup": (C.c_int, [C.c_void_p, _dp, _dp]),
     "pl_mpc_step": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl_mpc_set_plant": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pl_mpc_get_plant": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "pl_mpc_set_disturbance": (C.c_int, [C.c_void_p, _dp, _dp]),
     "pl_mpc_get_state": (C.c_int, [C.c_void_p, _dp]),
     "pl_mpc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "pl_mpc_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -418,6 +418,42 @@ class BatchedOCP:
     def mpc_step(self, k):
         _lib.check(_lib.lib().pl_mpc_step(self.h, int(k)))
 
+    PLANTS = {"nominal": 0, "aba": 1}
+
+    def mpc_set_plant(self, mode="aba", substeps=1):
+        """How the true state moves from one MPC step to the next: "nominal", the reference's own
+        loop, x_state <- integrate(x_state, DX[1]) (run_mpc.py:142), or "aba", forward dynamics
+        under node 0's commanded torques and forces and the base wrench of mpc_set_disturbance,
+        in ``substeps`` (1..16) explicit Euler steps of dt_min / substeps.  Not for
+        centroidal_vel (x = [h, q]).  A setting: needs no device."""
+        if mode not in self.PLANTS:
+            raise _lib.PinolocoError(f"plant mode {mode} unknown (choose from {sorted(self.PLANTS)})")
+        _lib.check(_lib.lib().pl_mpc_set_plant(self.h, self.PLANTS[mode], int(substeps)))
+
+    def mpc_get_plant(self):
+        """(mode, substeps) as mpc_set_plant takes them."""
+        mode, sub = C.c_int(), C.c_int()
+        _lib.check(_lib.lib().pl_mpc_get_plant(self.h, C.byref(mode), C.byref(sub)))
+        return {v: k for k, v in self.PLANTS.items()}[mode.value], sub.value
+
+    def mpc_set_disturbance(self, base_wrench=None, state_noise=None):
+        """Disturbances of the loop, held until the next call (None switches one off).
+        base_wrench [batch][6]: generalised force on v[0:6] of the free-flyer (linear then angular,
+        base frame), applied by the "aba" plant.  state_noise [batch][ndx]: the MPC plans from
+        x_init = state_integrate(x_state, noise) (run_mpc.py:79-82); mpc_state() stays the true
+        state.  New values replay the captured step; the caller draws the noise."""
+        def arr(a, width, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != (self.batch, width):
+                raise _lib.PinolocoError(f"{name} has shape {a.shape}, expected {(self.batch, width)}")
+            return a
+        w = arr(base_wrench, 6, "base_wrench")
+        z = arr(state_noise, self.layout.ndx, "state_noise")
+        _lib.check(_lib.lib().pl_mpc_set_disturbance(self.h, None if w is None else _lib.dptr(w),
+                                                     None if z is None else _lib.dptr(z)))
+
     def mpc_state(self):
         xs = np.zeros((self.batch, self.layout.nx))
         _lib.check(_lib.lib().pl_mpc_get_state(self.h, _lib.dptr(xs)))
