@@ -104,7 +104,8 @@ __device__ __forceinline__ f64x4 mfma4(double a, double b, f64x4 c) {
 //   side(B): independent work interleaved with pivot block B (k_fchain: slices of the
 //   previous node's tile store); the barriers order LDS only, so its global stores drain
 //   in the background
-template <int NB, int R, int NW, bool kTrack = false, class Side>
+//   kDirect: how a pivot column is updated (see below); k_fnode's u sweep sets it
+template <int NB, int R, int NW, bool kTrack = false, bool kDirect = false, class Side>
 __device__ __forceinline__ void sweep_split(double (&col)[4 * NB], double* pbC, double* pbO, int pbstride, int l,
                                             int ws, bool isC, int ncol, double* pmin, Side&& side) {
   constexpr int nblocks = R / 4;
@@ -211,12 +212,21 @@ __device__ __forceinline__ void sweep_split(double (&col)[4 * NB], double* pbC, 
       ts[1] = fma(-Lm[3][1], ts[3], fma(-Lm[2][1], ts[2], y1 * dinv[1]));
       ts[0] = fma(-Lm[3][0], ts[3], fma(-Lm[2][0], ts[2], fma(-Lm[1][0], ts[1], y0 * dinv[0])));
     }
+    // kDirect: a pivot column takes M_rj = (M_rP Q)_q = -M_rP nb directly (its old value times
+    // npv = 0) instead of col - M_rP (e_q - Q_:q), where the rounding of 1 - Q_qq costs the
+    // column eps |M_rq|, i.e. eps / Q_qq of its new value.  On a u block with large pivots
+    // (Q_qq ~ 1e-2: the tau nodes of whole_body_rnea) that form gave C^-1 the entrywise error of
+    // a LAPACK inverse but 20 - 60 x its residual |C^-1 C - I|, which the ADMM iterates inherit
+    // (tests/test_stage_kernels_gpu.py).  Non-pivot columns see the same bits either way.
+    // k_fchain's dx sweep keeps the earlier form: its residual is at the arithmetic's level
+    // already, and changing it alone or as well made no difference the stage tests see.
+    const double npv = 1.0 - pv;
     double t[4], nb[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const double qcol = m[p][0] * e[0] + m[p][1] * e[1] + m[p][2] * e[2] + m[p][3] * e[3];
-      nb[p] = fma(1.0 - pv, ts[p], qcol);
-      t[p] = nb[p] + e[p];
+      nb[p] = fma(npv, ts[p], qcol);
+      t[p] = kDirect ? nb[p] : nb[p] + e[p];
     }
     const bool own_blk = ws == ow;
 #pragma unroll
@@ -232,7 +242,8 @@ __device__ __forceinline__ void sweep_split(double (&col)[4 * NB], double* pbC, 
           const double2 rb = reinterpret_cast<const double2*>(pkC + 4 * (g0 + p))[1];
           const double h0 = fma(ra.y, t[1], ra.x * t[0]);
           const double h1 = fma(rb.y, t[3], rb.x * t[2]);
-          col[4 * j + p] = col[4 * j + p] - (h0 + h1);
+          if constexpr (kDirect) col[4 * j + p] = fma(col[4 * j + p], npv, -(h0 + h1));
+          else col[4 * j + p] = col[4 * j + p] - (h0 + h1);
         }
       }
     }
@@ -392,8 +403,8 @@ __global__ __launch_bounds__(NT) void k_fnode(PlDev d, int n, int m, int nnz, in
       }
     // pivots k >= U meet an identity pad (C) and zero rows (B^T): no-ops
     double pmin = 1.0;
-    sweep_split<NBU, UM, 2, HL>(col, pb, pb + 2 * 256 * set, 256, l, ws, set == 0, set == 0 ? UM : 64, &pmin,
-                                [](int) {});
+    sweep_split<NBU, UM, 2, HL, true>(col, pb, pb + 2 * 256 * set, 256, l, ws, set == 0, set == 0 ? UM : 64,
+                                      &pmin, [](int) {});
     if constexpr (HL) {
       if (w == 0 && l == 0 && !(pmin > 0.0)) d.ip_iflag[4 * b] = 1;
     }

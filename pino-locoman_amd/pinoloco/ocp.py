@@ -384,6 +384,14 @@ class BatchedOCP:
         v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
         _lib.check(_lib.lib().pl_debug_set(self.h, name.encode(), _lib.dptr(v), v.size))
 
+    def debug_admm(self, niter, reset=True):
+        """Stage tests: evaluate, scale and factor at the current x, then exactly ``niter`` ADMM
+        iterations of the selected kernel with no termination check and no line search
+        (reset: from x = z = y = 0, else from the iterates on the device).  debug("xa" | "za" |
+        "ya" | "As" | "Ps" | "qs" | "ls" | "us" | "rho" | "S" | "FS", ...) then read the scaled
+        iterates and data.  Call after set_params, set_x and init_solver."""
+        _lib.check(_lib.lib().pl_debug_admm(self.h, int(niter), int(bool(reset))))
+
     def lag_hess(self):
         """The interior point's Lagrangian Hessian blocks of the last Newton system (tests):
         [batch] list of csr n x n matrices (k_lag_hess, packed lower per node)."""

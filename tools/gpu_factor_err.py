@@ -20,32 +20,8 @@ ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pino-locoman_amd")]
 
 from conftest import golden  # noqa: E402
+from stage_ref import decode_S  # noqa: E402
 from test_gpu import _batched  # noqa: E402
-
-
-def decode_S(Sflat, s_off, nw, ntile, K):
-    """Lane-tile layout (state.h) -> dense symmetric nw x nw."""
-    T = ntile
-    M = np.zeros((4 * T, 4 * T))
-    for I in range(T):
-        for J in range(I + 1):
-            t = I * (I + 1) // 2 + J
-            ln, sl = t // K, t % K
-            for r in range(4):
-                for h in range(2):
-                    j = 2 * r + h
-                    base = s_off + ((sl * 8 + j) * 64 + ln) * 2
-                    M[4 * I + r, 4 * J + 2 * h] = Sflat[base]
-                    M[4 * I + r, 4 * J + 2 * h + 1] = Sflat[base + 1]
-    L = np.tril(M, -1)
-    D = np.diag(np.diag(M))
-    full = M.copy()
-    # off-diagonal tiles: upper = lower^T; diagonal tiles stored full
-    for I in range(T):
-        for J in range(I):
-            full[4 * J:4 * J + 4, 4 * I:4 * I + 4] = M[4 * I:4 * I + 4, 4 * J:4 * J + 4].T
-    del L, D
-    return full[:nw, :nw]
 
 
 def main():

@@ -11,29 +11,13 @@ import numpy as np
 import scipy.sparse as sp
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pino-locoman_amd"), os.path.join(ROOT, "tools")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pino-locoman_amd")]
 
 from conftest import golden  # noqa: E402
-from gpu_factor_err import decode_S  # noqa: E402
+from stage_ref import decode_S, fs_blocks, fs_offsets, gj_inv, rel  # noqa: E402
 from test_gpu import _batched  # noqa: E402
 
 LD = np.longdouble
-
-
-def gj_inv(M, dt=LD):
-    M = np.array(M, dtype=dt)
-    for k in range(M.shape[0]):
-        p = M[k, k]
-        r, c = M[k, :].copy(), M[:, k].copy()
-        M -= np.outer(c, r) / p
-        M[k, :], M[:, k] = r / p, c / p
-        M[k, k] = -1 / p
-    return -M
-
-
-def rel(a, ref):
-    ref = np.asarray(ref, dtype=np.float64)
-    return float(np.abs(np.asarray(a, dtype=np.float64) - ref).max() / max(np.abs(ref).max(), 1e-300))
 
 
 def main():
@@ -50,12 +34,7 @@ def main():
     Sall = bo.debug("S", B * S_stride).reshape(B, S_stride)
     nodes = bo.node_table()
     X = bo.layout.ndx
-    fs_off, fs = [], 0
-    for nd in nodes:
-        U = int(nd[1])
-        fs_off.append(fs)
-        fs = (fs + X * X + U * X + U * U + 31) & ~31
-    fs_stride = max(fs, 32)
+    fs_off, fs_stride = fs_offsets(nodes, X)
     FS = bo.debug("FS", B * fs_stride).reshape(B, fs_stride)
     rows, cols = bo.pattern()
     sig = bo.settings["sigma"]
@@ -73,8 +52,7 @@ def main():
             rec = dict(problem=b, node=i)
             o = fs_off[i]
             if U > 0:
-                Ag = FS[b][o:o + X * X].reshape(X, X)
-                Gg = FS[b][o + X * X:o + X * X + U * X].reshape(U, X)
+                Ag, Gg, Cg_low = fs_blocks(FS[b], o, X, U)  # C^-1: the lower triangle the chain reads
                 Cg = FS[b][o + X * X + U * X:o + X * X + U * X + U * U].reshape(U, U)
                 C_ld, B_ld, A_ld = Kt_ld[X:, X:], Kt_ld[:X, X:], Kt_ld[:X, :X]
                 Ci_ld = gj_inv(C_ld)
@@ -83,7 +61,6 @@ def main():
                 Ci_np = np.linalg.inv(Kt[X:, X:])
                 G_np = Ci_np @ Kt[:X, X:].T
                 Ap_np = Kt[:X, :X] - Kt[:X, X:] @ G_np
-                Cg_low = np.tril(Cg) + np.tril(Cg, -1).T  # the lower triangle the chain reads
                 rec.update(Cinv_gpu=rel(Cg_low, Ci_ld), Cinv_np=rel(Ci_np, Ci_ld), Cinv_gpu_asym=rel(Cg, Cg.T),
                            G_gpu=rel(Gg, G_ld), G_np=rel(G_np, G_ld), Ap_gpu=rel(Ag, Ap_ld), Ap_np=rel(Ap_np, Ap_ld))
             # S_i from the long-double chain on the same data

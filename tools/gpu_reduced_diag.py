@@ -19,9 +19,9 @@ ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "pino-locoman_amd"), os.path.join(ROOT, "tools")]
 
 from conftest import golden, make_robot  # noqa: E402
-from gpu_factor_err import decode_S  # noqa: E402
 from oracle.ocp import OracleOCP  # noqa: E402
 from oracle.osqp_ref import REFERENCE_SETTINGS, BlockReduced  # noqa: E402
+from stage_ref import decode_S  # noqa: E402
 from test_gpu import _batched, _kw, _settings  # noqa: E402
 
 
