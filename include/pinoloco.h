@@ -261,8 +261,9 @@ int pl_mpc_step(pl_ocp* o, int k);
  *     dynamics_whole_body_torque.py:55-103 builds it, re-expressed at each substep's q),
  *     q <- integrate(q, v h), v <- v + a h: explicit Euler with the old v, the OCP's own
  *     discretisation (ocp_whole_body_rnea.py:155-158).
- * There is no contact model: the forces are the commanded ones, world-aligned at the feet and,
- * where the robot has one, the external-force frame.  Works on a handle without a device;
+ * Without pl_mpc_set_contact (below) there is no contact model: the forces are the commanded
+ * ones, world-aligned at the feet and, where the robot has one, the external-force frame.  The
+ * setting works on a handle without a device;
  * substeps in [1, 16]; PL_PLANT_ABA needs x = [q, v]: every dynamics kind but centroidal_vel
  * (x = [h, q], dynamics_centroidal_vel.py:12-26).  The OSQP step re-captures its graph once
  * after a change; the interior-point step uses the plant alike. */
@@ -278,6 +279,47 @@ int pl_mpc_get_plant(const pl_ocp* o, int* mode, int* substeps);
  * the MPC plans from the measured state x_init = state_integrate(x_state, noise)
  * (run_mpc.py:79-82) while x_state stays the true state; under either plant. */
 int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, const double* state_noise);
+/* Ground contact at the feet and a joint PD loop, options of PL_PLANT_ABA (not a mode of their
+ * own).  With them the ground pushes back at the feet instead of the commanded forces, and the
+ * joint torque carries a PD term towards node 1 of the plan: the q, v, tau of the first nodes
+ * that compile_solution exports for a joint-level PD + feed-forward controller
+ * (ocp_whole_body_rnea.py:326-366).  Per problem and substep, for each foot e, in this order:
+ *   p = world position of the foot frame, u = its LOCAL_WORLD_ALIGNED linear velocity (at the
+ *       substep's q, v);  d = ground_z[e] - p.z
+ *   if !(d > 0):  f_e = 0; anchor[e].active = 0                     in the air; lift-off clears the anchor
+ *   else  fn = max(0, k_n d - d_n u.z)
+ *         if !anchor[e].active: anchor[e].xy = p.xy; active = 1     touchdown
+ *         ft = -k_t (p.xy - anchor[e].xy) - d_t u.xy
+ *         lim = mu fn;  nrm = sqrt(ft.x^2 + ft.y^2)
+ *         if nrm > lim:  ft *= lim / nrm;                           sliding: clamped to the cone,
+ *                        if k_t > 0: anchor[e].xy = p.xy + (ft + d_t u.xy) / k_t    the anchor dragged
+ *         f_e = (ft.x, ft.y, fn)                                    world-aligned at the foot frame
+ *   tau_j = tau_cmd + kp (q_des - q_j) + kd (v_des - v_j)
+ *   a = ABA(q, v, [w_b; tau_j], [f_ground(feet) | f_cmd(ext frame)]); q <- integrate(q, v h); v <- v + a h
+ * tau_cmd, f_cmd: node 0 of the retract, as above; q_des, v_des: the joint parts of node 1 of the
+ * same retract (believed state), held over the step.  The external-force frame keeps its command.
+ * Integrator, h and substeps are those of PL_PLANT_ABA.  The ground is flat under each foot at
+ * its own height ground_z[batch][n_feet] (steps and holes).  The anchors ([batch][n_feet][3]:
+ * x, y, active) are plant state: they persist across substeps and MPC steps, and pl_mpc_setup
+ * clears them.  The explicit damping term is the stability limit: h d_n / m_foot < 2 for the
+ * lightest foot link; nothing hides it, a plant past it diverges.
+ * prm [batch] and ground_z [batch][n_feet]; prm == NULL switches contact and PD off (ground_z
+ * ignored).  Refused: k_n <= 0, any negative or non-finite field, centroidal_vel, a handle
+ * without a device.  Set while the plant is PL_PLANT_NOMINAL, it is stored and takes effect
+ * when PL_PLANT_ABA is selected.  New values and ground heights replay the captured step;
+ * switching on or off re-captures once. */
+typedef struct { double k_n, d_n, k_t, d_t, mu, kp, kd, pad; } pl_contact_params;   /* one per problem */
+int pl_mpc_set_contact(pl_ocp* o, const pl_contact_params* prm, const double* ground_z);
+/* any pointer may be NULL: on (0/1), anchors [batch][n_feet][3], the ground forces of the last
+ * substep [batch][n_feet][3] */
+int pl_mpc_get_contact(pl_ocp* o, int* on, double* anchors, double* forces);
+/* One problem's plant step on the host, the same pl::plant_step the kernel runs: p [np], x [n]
+ * (the iterate), base_wrench [6] or NULL, prm or NULL (the plain PL_PLANT_ABA step; ground_z and
+ * anchors are then not read), anchors [n_feet][3] in/out, x_state [nx] in/out, forces
+ * [n_feet][3] out or NULL.  Works on a handle without a device. */
+int pl_mpc_plant_host(const pl_ocp* o, const double* p, const double* x, const double* base_wrench,
+                      const pl_contact_params* prm, const double* ground_z, double* anchors, int substeps,
+                      double* x_state, double* forces);
 int pl_mpc_get_state(pl_ocp* o, double* x_state);
 /* Solver stats of the last MPC step's (last) SQP iteration, as pl_ocp_solve reports. */
 int pl_mpc_get_stats(pl_ocp* o, pl_stats* stats);

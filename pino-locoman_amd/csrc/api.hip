@@ -7,6 +7,7 @@
 // (optimization/ocp.py:38-44, 103-198, 283, 305) and the device programs are built in
 // api_build.hip; the CasADi external-function ABI is api_casadi.hip.
 #include "api_internal.h"
+#include "plant.h"
 #include "retract.h"
 
 #include <map>
@@ -248,6 +249,7 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   h.plant_mode = PL_PLANT_NOMINAL;  // pl_mpc_set_plant / pl_mpc_set_disturbance: the loop follows its own plan
   h.plant_substeps = 1;
   h.plant_noise_on = 0;
+  h.plant_contact_on = 0;
   h.solver = PL_SOLVER_OSQP;
   // Fatrop settings of the reference (ocp.py:254-262) + the restatement's constants
   // (oracle/ip_ref.py IP_SETTINGS)
@@ -393,6 +395,11 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   // pointers, part of the MPC graph's launches, never change
   rc |= dalloc(o, &D.plant_w, B * 6);
   rc |= dalloc(o, &D.plant_noise, B * (size_t)h.ndx);
+  // the plant's contact data (pl_mpc_set_contact), zeroed, for the same reason
+  rc |= dalloc(o, &D.plant_cprm, B);
+  rc |= dalloc(o, &D.plant_gz, B * (size_t)h.oc.nfeet);
+  rc |= dalloc(o, &D.plant_anchor, B * (size_t)h.oc.nfeet * 3);
+  rc |= dalloc(o, &D.plant_cf, B * (size_t)h.oc.nfeet * 3);
   D.dbg = nullptr;
   if (h.debug_paths & PL_PATH_ADMM_TIMING) rc |= dalloc(o, &D.dbg, B * 40);
   if (rc) { pl_ocp_destroy(o); return -2; }
@@ -1142,6 +1149,10 @@ extern "C" int pl_mpc_setup(pl_ocp* o, const double* x_state, const double* t0) 
   PlOcpHandle* h = &o->h;
   PL_CHECK_HIP(hipMemcpyAsync(h->d.xstate, x_state, (size_t)h->B * h->nx * 8, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipMemcpyAsync(h->d.t0, t0, (size_t)h->B * 8, hipMemcpyHostToDevice, h->stream));
+  // a new loop: no foot has touched down yet (the contact plant's anchors and last forces)
+  const size_t cb = (size_t)h->B * h->oc.nfeet * 3 * 8;
+  PL_CHECK_HIP(hipMemsetAsync(h->d.plant_anchor, 0, cb, h->stream));
+  PL_CHECK_HIP(hipMemsetAsync(h->d.plant_cf, 0, cb, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->ip_lam_warm = 0;  // the loop's first solve has no lam_g yet (ocp.py:198)
   return 0;
@@ -1182,6 +1193,80 @@ extern "C" int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, cons
   if (state_noise) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_noise, state_noise, nb, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->plant_noise_on = state_noise ? 1 : 0;  // off: k_mpc_prepare's plain copy of x_state
+  return 0;
+}
+
+// Ground contact at the feet and the joint PD loop of PL_PLANT_ABA (plant.h).  The switch is
+// host state inside the graph key; parameters, ground heights, anchors and last forces are
+// device data, so new values replay.
+static_assert(sizeof(pl_contact_params) == sizeof(PlContact), "pl_contact_params and PlContact are one layout");
+
+static int contact_check(const char* who, const pl_ocp* o, const pl_contact_params* prm, int count) {
+  if (PL_IS_CV(o->h.oc.dyn)) {
+    pl_set_error("%s: the contact plant is defined on x = [q, v]; centroidal_vel has x = [h, q]", who);
+    return -1;
+  }
+  static const char* const names[7] = {"k_n", "d_n", "k_t", "d_t", "mu", "kp", "kd"};
+  for (int b = 0; prm && b < count; ++b) {
+    const double* f = &prm[b].k_n;
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(f[k]) || f[k] < 0.0) {
+        pl_set_error("%s: problem %d: %s = %g is negative or not finite", who, b, names[k], f[k]);
+        return -1;
+      }
+    if (!(prm[b].k_n > 0.0)) {
+      pl_set_error("%s: problem %d: k_n = %g must be positive", who, b, prm[b].k_n);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+extern "C" int pl_mpc_set_contact(pl_ocp* o, const pl_contact_params* prm, const double* ground_z) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (contact_check("pl_mpc_set_contact", o, prm, o->h.B)) return -1;
+  if (prm && !ground_z) { pl_set_error("pl_mpc_set_contact: ground_z is null"); return -1; }
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (prm) {
+    PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_cprm, prm, (size_t)h->B * sizeof(PlContact), hipMemcpyHostToDevice, h->stream));
+    PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_gz, ground_z, (size_t)h->B * h->oc.nfeet * 8, hipMemcpyHostToDevice, h->stream));
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  }
+  h->plant_contact_on = prm ? 1 : 0;
+  return 0;
+}
+
+extern "C" int pl_mpc_get_contact(pl_ocp* o, int* on, double* anchors, double* forces) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  const size_t cb = (size_t)h->B * h->oc.nfeet * 3 * 8;
+  if (on) *on = h->plant_contact_on;
+  if (anchors) PL_CHECK_HIP(hipMemcpyAsync(anchors, h->d.plant_anchor, cb, hipMemcpyDeviceToHost, h->stream));
+  if (forces) PL_CHECK_HIP(hipMemcpyAsync(forces, h->d.plant_cf, cb, hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int pl_mpc_plant_host(const pl_ocp* o, const double* p, const double* x, const double* base_wrench,
+                                 const pl_contact_params* prm, const double* ground_z, double* anchors, int substeps,
+                                 double* x_state, double* forces) {
+  if (!o || !p || !x || !x_state) { pl_set_error("pl_mpc_plant_host: null argument"); return -1; }
+  if (substeps < 1 || substeps > 16) { pl_set_error("pl_mpc_plant_host: substeps %d outside [1, 16]", substeps); return -1; }
+  if (contact_check("pl_mpc_plant_host", o, prm, 1)) return -1;
+  if (prm && (!ground_z || !anchors)) { pl_set_error("pl_mpc_plant_host: contact needs ground_z and anchors"); return -1; }
+  const PlOcpHandle& h = o->h;
+  if (!prm) {
+    pl::plant_step<false>(h.model, h.oc, h.oc.dyn, o->nodes.data(), h.N, p, x, base_wrench, substeps, x_state);
+    return 0;
+  }
+  double fg[3 * PL_MAXFEET] = {0.0};
+  PlContact c;
+  memcpy(&c, prm, sizeof(c));
+  pl::plant_step<true>(h.model, h.oc, h.oc.dyn, o->nodes.data(), h.N, p, x, base_wrench, substeps, x_state, &c, ground_z,
+                       anchors, fg);
+  if (forces)
+    for (int k = 0; k < 3 * h.oc.nfeet; ++k) forces[k] = fg[k];
   return 0;
 }
 

@@ -840,11 +840,24 @@ struct NoBaseWrench {};
 template <class S> PL_HD S aba_root_force(const NoBaseWrench&, int, const S& pA) { return -pA; }
 template <class S, class InW> PL_HD S aba_root_force(const InW& w, int k, const S& pA) { return w[k] - pA; }
 
+// Where the world-aligned point force at contact frame e comes from.  An array source (the OCP's
+// dynamics, the plant's commanded forces) is indexed, forces[3 e + c].  A source that computes
+// the force from the frame's motion (the plant's ground, plant.h) declares
+// AbaForceSource<InF>::kFromMotion and overloads aba_point_force, which then gets what the first
+// pass has at hand for the frame's joint j: oR[j], vv[j] and the joint's world position, the
+// only quantity carried for this use (op, one entry for every other source).
+template <class InF> struct AbaForceSource { static constexpr bool kFromMotion = false; };
+template <class S, class InF>
+PL_HD void aba_point_force(const InF& forces, int e, const PlFrameRef&, const S*, const S*, const S*, S* fw) {
+  for (int k = 0; k < 3; ++k) fw[k] = forces[3 * e + k];
+}
+
 template <class S, class InT, class InF, class InW = NoBaseWrench>
 PL_HD void aba_forward(const PlModel& M, const PlOcpConst& O, const S* q, const S* v, const InT& tau_j,
                        const InF& forces, S* ddq, const InW& base_wrench = InW()) {
   const int nb = M.njoints;
-  S lR[PL_MAXJ][9], lp[PL_MAXJ][3], oR[PL_MAXJ][9];
+  constexpr bool kPos = AbaForceSource<InF>::kFromMotion;
+  S lR[PL_MAXJ][9], lp[PL_MAXJ][3], oR[PL_MAXJ][9], op[kPos ? PL_MAXJ : 1][3];
   S vv[PL_MAXJ][6], cc[PL_MAXJ][6], pA[PL_MAXJ][6], Ia[PL_MAXJ][36];
   for (int j = 1; j < nb; ++j) {
     const int par = M.parent[j];
@@ -869,6 +882,15 @@ PL_HD void aba_forward(const PlModel& M, const PlOcpConst& O, const S* q, const 
       act_inv_motion(lR[j], lp[j], vv[par], vv[j]);
       for (int k = 0; k < 6; ++k) vv[j][k] += vJ[k];
     }
+    if constexpr (kPos) {
+      if (par == 0) {
+        for (int k = 0; k < 3; ++k) op[j][k] = lp[j][k];
+      } else {
+        S t[3];
+        matvec(oR[par], lp[j], t);
+        for (int k = 0; k < 3; ++k) op[j][k] = op[par][k] + t[k];
+      }
+    }
     {
       S t1[3], t2[3], t3[3];
       cross3(vv[j] + 3, vJ, t1);
@@ -883,7 +905,8 @@ PL_HD void aba_forward(const PlModel& M, const PlOcpConst& O, const S* q, const 
     for (int e = 0; e < O.nee; ++e) {
       const PlFrameRef& F = (e < O.nfeet) ? O.feet[e] : O.ext;
       if (F.joint != j) continue;
-      S fw[3] = {forces[3 * e], forces[3 * e + 1], forces[3 * e + 2]};
+      S fw[3];
+      aba_point_force(forces, e, F, oR[j], op[kPos ? j : 0], vv[j], fw);
       S fl[3];
       mattvec(oR[j], fw, fl);
       S pf[3] = {S(F.p[0]), S(F.p[1]), S(F.p[2])};

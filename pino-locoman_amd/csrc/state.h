@@ -161,6 +161,12 @@ struct PlIpInfo {
   double alphas[PL_IP_MAXFILT];    // accepted step of each iteration
 };
 
+// pl_contact_params (include/pinoloco.h), one per problem: ground stiffness and damping (normal,
+// tangential), friction coefficient, joint PD gains (plant.h)
+struct PlContact {
+  double k_n, d_n, k_t, d_t, mu, kp, kd, pad;
+};
+
 struct PlDev {
   // shared structure
   PlModel* model;
@@ -235,6 +241,11 @@ struct PlDev {
   double* xstate;    // per-problem current state x_init (nx)
   double* plant_w;   // [B][6] base wrench of the plant (pl_mpc_set_disturbance; zero rows: none), k_plant.hip
   double* plant_noise;  // [B][ndx] state noise of the measured x_init (read while PlOcpHandle::plant_noise_on)
+  // ground contact and joint PD of the plant (pl_mpc_set_contact; read while PlOcpHandle::plant_contact_on)
+  PlContact* plant_cprm;   // [B] parameters
+  double* plant_gz;        // [B][n_feet] ground height under each foot
+  double* plant_anchor;    // [B][n_feet][3] tangential anchors (x, y, active): plant state, cleared by pl_mpc_setup
+  double* plant_cf;        // [B][n_feet][3] ground forces of the last substep
   double* dbg;       // optional kernel timing [B][16] (PL_ADMM_TIMING=1 at handle creation)
   // interior point [B][m] (allocated by pl_ocp_set_solver(o, PL_SOLVER_IP))
   double* ip_s;      // slacks of the inequality rows
@@ -345,6 +356,7 @@ struct PlOcpHandle {
   int plant_mode;                   // PL_PLANT_NOMINAL (k_mpc_finish) or PL_PLANT_ABA (k_plant)
   int plant_substeps;               // Euler substeps of dt_min, [1, 16]
   int plant_noise_on;               // 1: k_mpc_prepare writes x_init = state_integrate(x_state, noise)
+  int plant_contact_on;             // 1: PL_PLANT_ABA runs k_plant's contact instantiation (pl_mpc_set_contact)
   PlDev d;
   // host copies of the structure
   int* h_nodes_raw;

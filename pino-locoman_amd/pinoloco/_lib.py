@@ -64,6 +64,11 @@ class IpStats(C.Structure):
                 ("ref_solves", C.c_int), ("pad", C.c_int)]
 
 
+class ContactParams(C.Structure):
+    _fields_ = [("k_n", C.c_double), ("d_n", C.c_double), ("k_t", C.c_double), ("d_t", C.c_double),
+                ("mu", C.c_double), ("kp", C.c_double), ("kd", C.c_double), ("pad", C.c_double)]
+
+
 EXPORTS = {
     "pl_last_error": (C.c_char_p, []),
     "pl_version": (C.c_int, []),
@@ -104,6 +109,10 @@ EXPORTS = {
     "pl_mpc_set_plant": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_mpc_get_plant": (C.c_int, [C.c_void_p, _ip, _ip]),
     "pl_mpc_set_disturbance": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "pl_mpc_set_contact": (C.c_int, [C.c_void_p, C.POINTER(ContactParams), _dp]),
+    "pl_mpc_get_contact": (C.c_int, [C.c_void_p, _ip, _dp, _dp]),
+    "pl_mpc_plant_host": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(ContactParams), _dp, _dp, C.c_int, _dp,
+                                    _dp]),
     "pl_mpc_get_state": (C.c_int, [C.c_void_p, _dp]),
     "pl_mpc_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "pl_mpc_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -152,6 +152,19 @@ def default_weights(robot, dynamics, layout):
     return Q, R, W
 
 
+def contact_defaults(robot, penetration=0.005, zeta=0.3, mu=None, kp=0.0, kd=0.0, n_feet=4):
+    """Contact parameters of BatchedOCP.mpc_set_contact for ``robot``: a ground that carries the
+    weight on n_feet feet at ``penetration`` metres, k_n = m g / (n_feet penetration), with damping
+    ratio ``zeta`` of a quarter of the mass on one foot's spring, d_n = 2 zeta sqrt(k_n m / n_feet);
+    k_t = k_n, d_t = d_n; mu defaults to the OCP description's 0.7.  The plant integrates the
+    damping explicitly: it is stable only while h d_n / m_foot < 2 for the lightest foot link
+    (h = dt_min / substeps), which on Go2 and B2G means zeta = 0.3 at 16 substeps, not zeta = 1."""
+    m = float(robot.mass)
+    k_n = m * 9.81 / (n_feet * penetration)
+    d_n = 2.0 * zeta * np.sqrt(k_n * m / n_feet)
+    return dict(k_n=k_n, d_n=d_n, k_t=k_n, d_t=d_n, mu=0.7 if mu is None else float(mu), kp=float(kp), kd=float(kd))
+
+
 class BatchedOCP:
     """A batch of independent OCPs of one (robot, dynamics, N) on one GPU."""
 
@@ -165,6 +178,7 @@ class BatchedOCP:
         self.robot = robot
         self.dynamics = dynamics
         self.batch = batch
+        self.mu = float(mu)
         self.layout = Layout(robot, dynamics, nodes, tau_nodes, include_base, include_acc)
         self.model_h = ModelCache.get(robot.model)
         s = dict(OSQP_SETTINGS)
@@ -461,6 +475,90 @@ class BatchedOCP:
         z = arr(state_noise, self.layout.ndx, "state_noise")
         _lib.check(_lib.lib().pl_mpc_set_disturbance(self.h, None if w is None else _lib.dptr(w),
                                                      None if z is None else _lib.dptr(z)))
+
+    CONTACT_FIELDS = ("k_n", "d_n", "k_t", "d_t", "mu", "kp", "kd")
+    N_FEET = 4
+
+    def _contact_structs(self, params, count):
+        """``count`` pl_contact_params from a dict of CONTACT_FIELDS, each a scalar or a [count] array."""
+        unknown = sorted(set(params) - set(self.CONTACT_FIELDS))
+        missing = [k for k in self.CONTACT_FIELDS if k not in params]
+        if unknown or missing:
+            raise _lib.PinolocoError(f"contact params: unknown fields {unknown}, missing fields {missing} "
+                                     f"(fields: {self.CONTACT_FIELDS})")
+        prm = (_lib.ContactParams * count)()
+        for name in self.CONTACT_FIELDS:
+            a = np.asarray(params[name], dtype=np.float64)
+            if a.shape not in ((), (count,)):
+                raise _lib.PinolocoError(f"contact params: {name} has shape {a.shape}, expected a scalar or {(count,)}")
+            for b, val in enumerate(np.broadcast_to(a, (count,))):
+                setattr(prm[b], name, float(val))
+        return prm
+
+    def contact_defaults(self, penetration=0.005, zeta=0.3, mu=None, kp=0.0, kd=0.0):
+        """contact_defaults of this OCP's robot, with the OCP's own friction coefficient by default."""
+        return contact_defaults(self.robot, penetration, zeta, self.mu if mu is None else mu, kp, kd)
+
+    def ground_under_feet(self, x_state, penetration=0.005):
+        """[batch][n_feet] ground heights that put every foot of each state ``penetration`` deep: the
+        foot-frame heights (get_frame_position, host evaluation) plus ``penetration``.  x_state: one
+        state or configuration, or [batch] of them."""
+        from .dynamics import Dynamics
+        xs = np.atleast_2d(np.asarray(x_state, dtype=np.float64))
+        if xs.shape[0] not in (1, self.batch) or xs.shape[1] not in (self.robot.nq, self.layout.nx):
+            raise _lib.PinolocoError(f"x_state has shape {np.shape(x_state)}, expected [{self.batch}][{self.layout.nx}]")
+        q = np.ascontiguousarray(np.broadcast_to(xs[:, :self.robot.nq], (self.batch, self.robot.nq)))
+        dyn = Dynamics(self.robot, device=-1)
+        z = [dyn.get_frame_position(f)(q).reshape(self.batch, 3)[:, 2] for f in self.robot.foot_frames]
+        return np.stack(z, -1) + float(penetration)
+
+    def mpc_set_contact(self, params=None, ground_z=None):
+        """Ground contact at the feet and the joint PD loop of the "aba" plant (pl_mpc_set_contact).
+        params: a dict of CONTACT_FIELDS (contact_defaults), each field a scalar or a [batch] array;
+        ground_z [batch][n_feet]: the ground height under each foot (ground_under_feet).  None
+        switches both off.  Stored while the plant is "nominal"; new values replay the captured
+        step, switching on or off re-captures once."""
+        if params is None:
+            _lib.check(_lib.lib().pl_mpc_set_contact(self.h, None, None))
+            return
+        prm = self._contact_structs(params, self.batch)
+        gz = np.ascontiguousarray(np.asarray(ground_z if ground_z is not None else (), dtype=np.float64))
+        if gz.shape != (self.batch, self.N_FEET):
+            raise _lib.PinolocoError(f"ground_z has shape {gz.shape}, expected {(self.batch, self.N_FEET)}")
+        _lib.check(_lib.lib().pl_mpc_set_contact(self.h, prm, _lib.dptr(gz)))
+
+    def mpc_get_contact(self):
+        """{"on": bool, "anchors": [batch][n_feet][3] (x, y, active), "forces": [batch][n_feet][3],
+        the ground forces of the last substep}."""
+        on = C.c_int()
+        anchors, forces = np.zeros((self.batch, self.N_FEET, 3)), np.zeros((self.batch, self.N_FEET, 3))
+        _lib.check(_lib.lib().pl_mpc_get_contact(self.h, C.byref(on), _lib.dptr(anchors), _lib.dptr(forces)))
+        return {"on": bool(on.value), "anchors": anchors, "forces": forces}
+
+    def mpc_plant_host(self, p, x, x_state, substeps=1, base_wrench=None, params=None, ground_z=None, anchors=None):
+        """One problem's "aba" plant step on the host, the code the kernel runs (pl_mpc_plant_host):
+        parameters p [np], iterate x [n], true state x_state [nx]; params (a dict of scalar
+        CONTACT_FIELDS), ground_z [n_feet] and anchors [n_feet][3] (None: none touched down) add
+        contact and PD.  Returns (new state, new anchors, ground forces [n_feet][3]); without
+        params the anchors come back as given and the forces zero.  Needs no device."""
+        def arr(a, shape, name):
+            a = np.array(a, dtype=np.float64)
+            if a.shape != shape:
+                raise _lib.PinolocoError(f"{name} has shape {a.shape}, expected {shape}")
+            return np.ascontiguousarray(a)
+        p, x = arr(p, (self.np,), "p"), arr(x, (self.n,), "x")
+        xs = arr(x_state, (self.layout.nx,), "x_state")
+        w = None if base_wrench is None else arr(base_wrench, (6,), "base_wrench")
+        anc = arr(np.zeros((self.N_FEET, 3)) if anchors is None else anchors, (self.N_FEET, 3), "anchors")
+        forces = np.zeros((self.N_FEET, 3))
+        prm = gz = None
+        if params is not None:
+            prm = self._contact_structs(params, 1)
+            gz = arr(ground_z if ground_z is not None else (), (self.N_FEET,), "ground_z")
+        _lib.check(_lib.lib().pl_mpc_plant_host(self.h, _lib.dptr(p), _lib.dptr(x), None if w is None else _lib.dptr(w),
+                                                prm, None if gz is None else _lib.dptr(gz), _lib.dptr(anc),
+                                                int(substeps), _lib.dptr(xs), _lib.dptr(forces)))
+        return xs, anc, forces
 
     def mpc_state(self):
         xs = np.zeros((self.batch, self.layout.nx))

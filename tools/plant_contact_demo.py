@@ -1,0 +1,86 @@
+"""Closed-loop demo of the contact plant: does the MPC's trot stay up on the ground of mpc_set_contact?
+
+Go2 whole_body_rnea, N = 20, B = 64, trot, 200 MPC steps (2 s) from the standing pose, "aba" plant
+with 16 substeps, contact_defaults with PD (kp 40, kd 1), the ground 5 mm under the standing feet.
+Two runs, one problem per value:
+  push  a lateral base push (world-y at the start, base frame) for 0.1 s from step 50, ramped
+        across the batch from 0 to --push-max newtons
+  mu    the ground's friction coefficient ramped from 0.1 to 1.0 (the OCP keeps planning with 0.7)
+Per problem: whether the state stayed finite and the base within 10 cm of its starting height over
+the whole run, and the largest height deviation.  Writes profiles/plant/contact_demo.json (--out).
+Nothing here is a pass bar: it records what the loop does on this ground.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.normpath(os.path.join(HERE, ".."))
+sys.path.insert(0, os.path.join(ROOT, "pino-locoman_amd"))
+
+
+def run(kind, args):
+    from pinoloco import robots
+    from pinoloco.ocp import BatchedOCP
+    from pinoloco.synthetic import initial_guess, problem_values
+    B, N = args.batch, args.nodes
+    R = robots.ROBOTS["go2"]()
+    R.set_gait_sequence("trot", 0.8)
+    bo = BatchedOCP(R, "whole_body_rnea", N, batch=B, device=0)
+    lay = bo.layout
+    vals, _, _ = problem_values(R, "whole_body_rnea", N, 0, lay)
+    x0 = np.concatenate([R.q0, np.zeros(R.nv)])
+    vals["x_init"] = x0
+    bo.set_params(np.tile(lay.pack(vals), (B, 1)))
+    bo.set_x(np.tile(initial_guess(R, lay, vals["n_contacts"]), (B, 1)))
+    bo.init_solver()
+    bo.mpc_setup(np.tile(x0, (B, 1)), np.zeros(B))
+    bo.mpc_set_plant("aba", args.substeps)
+    ramp = np.linspace(0.0, 1.0, B)
+    c = bo.contact_defaults(kp=args.kp, kd=args.kd)
+    if kind == "mu":
+        c["mu"] = 0.1 + 0.9 * ramp
+    bo.mpc_set_contact(c, bo.ground_under_feet(x0, 0.005))
+    W = np.zeros((B, 6))
+    W[:, 1] = args.push_max * ramp
+    finite, dz = np.ones(B, bool), np.zeros(B)
+    for k in range(args.steps):
+        if kind == "push" and k == 50:
+            bo.mpc_set_disturbance(base_wrench=W)
+        if kind == "push" and k == 60:
+            bo.mpc_set_disturbance()
+        bo.mpc_step(k)
+        xs = bo.mpc_state()
+        ok = np.all(np.isfinite(xs), axis=1)
+        finite &= ok
+        dz = np.where(ok, np.maximum(dz, np.abs(xs[:, 2] - x0[2])), dz)
+    feet = bo.mpc_get_contact()["anchors"][:, :, 2].sum(1)
+    status = bo.mpc_stats()["status"]
+    bo.close()
+    up = finite & (dz < 0.10)
+    return {"value": (W[:, 1] if kind == "push" else c["mu"]).tolist(), "finite": finite.tolist(),
+            "within_10cm": up.tolist(), "max_height_dev": dz.tolist(), "feet_on_ground_at_end": feet.tolist(),
+            "final_xy": xs[:, :2].tolist(), "solver_status_at_end": status.tolist(),
+            "survived": int(up.sum()), "of": B}
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--nodes", type=int, default=20)
+ap.add_argument("--steps", type=int, default=200)
+ap.add_argument("--substeps", type=int, default=16)
+ap.add_argument("--kp", type=float, default=40.0)
+ap.add_argument("--kd", type=float, default=1.0)
+ap.add_argument("--push-max", type=float, default=100.0)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plant", "contact_demo.json"))
+a = ap.parse_args()
+res = {"setup": {k: getattr(a, k) for k in ("batch", "nodes", "steps", "substeps", "kp", "kd", "push_max")}}
+for kind in ("push", "mu"):
+    res[kind] = run(kind, a)
+    print(kind, "survived", res[kind]["survived"], "of", res[kind]["of"], flush=True)
+os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+with open(a.out, "w") as f:
+    f.write(json.dumps(res, indent=1) + "\n")

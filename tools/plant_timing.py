@@ -3,9 +3,11 @@
 Two halves, because a kernel's own time comes from the profiler's kernel trace, in a run of its own:
 
   rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- \
-      python tools/plant_timing.py run --mode aba --substeps 4 [robot dynamics N B]
+      python tools/plant_timing.py run --mode aba --substeps 4 [--contact] [robot dynamics N B]
       an MPC loop (3 warm-up steps + 10) with the plant as given; eager launches (no_mpc_graph), so
       every launch is one dispatch of the trace.  The plant runs on the solved iterate of each step.
+      --contact adds the ground contact and joint PD of mpc_set_contact (k_plant's contact
+      instantiation; profiles/plant/plant_contact_timing.json).
   python tools/plant_timing.py parse LABEL=DIR [LABEL=DIR ...] [--out FILE]
       per label the median / min / max duration of the last 10 k_plant or k_mpc_finish dispatches
       of DIR's *kernel_trace.csv, as one JSON.
@@ -44,11 +46,21 @@ def run(args):
     bo.mpc_set_plant(args.mode, args.substeps)
     if args.mode == "aba":  # a push on every problem: the wrench is read either way
         bo.mpc_set_disturbance(base_wrench=np.random.default_rng(5).normal(size=(B, 6)) * 10.0)
+    if args.contact:
+        # the ground under each problem's own feet.  The defaults of this tool are a soft, lightly
+        # damped ground (5 cm, zeta 0.05) that stays inside the explicit damping limit at one
+        # substep too, so that every timed run steps finite states; the kernel's work per substep
+        # does not depend on the values.
+        c = bo.contact_defaults(penetration=args.penetration, zeta=args.zeta, kp=40.0, kd=1.0)
+        bo.mpc_set_contact(c, bo.ground_under_feet(XS, args.penetration))
     for k in range(WARM + STEPS):
         bo.mpc_step(k)
     xs = bo.mpc_state()
-    print(json.dumps({"mode": args.mode, "substeps": args.substeps, "shape": args.shape, "lib": _lib.LIB_PATH,
-                      "lib_src_sha256": _lib.build_sha(), "finite": bool(np.all(np.isfinite(xs)))}))
+    out = {"mode": args.mode, "substeps": args.substeps, "contact": bool(args.contact), "shape": args.shape,
+           "lib": _lib.LIB_PATH, "lib_src_sha256": _lib.build_sha(), "finite": bool(np.all(np.isfinite(xs)))}
+    if args.contact:
+        out["feet_on_ground"] = float(bo.mpc_get_contact()["anchors"][:, :, 2].mean())
+    print(json.dumps(out))
     bo.close()
 
 
@@ -86,6 +98,9 @@ sub = ap.add_subparsers(dest="cmd", required=True)
 r = sub.add_parser("run")
 r.add_argument("--mode", default="aba", choices=["aba", "nominal"])
 r.add_argument("--substeps", type=int, default=1)
+r.add_argument("--contact", action="store_true", help="ground contact and joint PD (mpc_set_contact), aba only")
+r.add_argument("--penetration", type=float, default=0.05)
+r.add_argument("--zeta", type=float, default=0.05)
 r.add_argument("shape", nargs="*", default=["b2g", "whole_body_rnea", "50", "1024"])
 p = sub.add_parser("parse")
 p.add_argument("dirs", nargs="+")
