@@ -372,6 +372,78 @@ int pl_mpc_graph_info(const pl_ocp* o, long long* out);
  * Opti branch (compile_solver = False, run_mpc.py:115-143 through OCP.solve): warm_start() passes
  * the previous solve's lam_g (ocp_whole_body_rnea.py:234-235, ocp.py:373). */
 int pl_mpc_set_ip_lam(pl_ocp* o, int carry);
+
+/* Rollout on the device: a log of what happened at every MPC step, a per-problem outcome, pushes
+ * in step windows and a run of steps, with nothing crossing to the host until the caller reads.
+ * All of it is off by default, and then pl_mpc_step launches exactly what it launches without it.
+ *
+ * While the log is on, pl_mpc_step ends with one more launch, outside the captured step (as the
+ * gait / warm-start kernel before it), so starting and stopping the log never re-captures.  It
+ * writes one row of doubles per problem, fields in this order:
+ *   x_init [nx]            the believed state the step planned from (with the state noise)
+ *   u0 [nu_0]              the iterate's node-0 inputs, as pl_mpc_download exports them
+ *   stats [8]              status, admm_iters, ls_accepted, ls_alpha, viol_max, f, pri_res, dua_res
+ *                          of pl_mpc_get_stats for this step
+ *   x_state [nx]           the true state after the plant (the state of step k + 1)
+ *   ground_f [n_feet * 3]  the ground forces of the last substep (zero while contact is off)
+ *   anchor_active [n_feet] 1 where the foot's anchor is set
+ * into the log [slot][batch][row].  The s-th step since pl_mpc_log_start (s = 0, 1, ...) is
+ * recorded when s % every == 0, into the next of `capacity` slots; with every slot taken it is
+ * counted as dropped.  The metrics are updated at every step, recorded or not:
+ *   steps            steps seen
+ *   first_nonfinite  the first k whose x_state holds a non-finite entry, else -1
+ *   first_out        the first k with a finite x_state and |z - z_ref| > dz_tol or c_z < cz_min,
+ *                    else -1: z the base height, c_z = 1 - 2 (q_x^2 + q_y^2) of the base quaternion
+ *                    (x, y, z, w), the cosine of the base's tilt; z_ref the base height of x_state
+ *                    when the log was started (read on the device)
+ *   max_dz, min_cz   extrema of |z - z_ref| and c_z over the finite states (start values 0 and 1)
+ *   n_not_solved     steps with status != 1;  n_ls_rejected  steps with ls_accepted == 0
+ *   max_viol         largest finite viol_max (start value 0) */
+typedef struct {
+  int steps, first_nonfinite, first_out, n_not_solved, n_ls_rejected, pad;
+  double max_dz, min_cz, max_viol;
+} pl_mpc_metrics_t;
+/* Allocates or reuses the buffers and resets cursor, counters and metrics; after pl_mpc_setup.
+ * capacity == 0: metrics only.  dz_tol, cz_min [batch], either may be NULL: never out by that
+ * test.  Refused: capacity < 0, every < 1, a non-finite tolerance, a handle without a device;
+ * a failed allocation is an error return. */
+int pl_mpc_log_start(pl_ocp* o, long long capacity, int every, const double* dz_tol, const double* cz_min);
+/* Stops recording (log and metrics); both stay readable. */
+int pl_mpc_log_stop(pl_ocp* o);
+/* out[17]: width and offset (doubles) inside a row of each field in the order above (out[2 f],
+ * out[2 f + 1]), then the row width, capacity, every, recorded, dropped.  The field sizes work
+ * on a handle without a device (the last four are then 0). */
+int pl_mpc_log_sizes(const pl_ocp* o, long long* out /*[17]*/);
+/* Slots [first_slot, first_slot + count) into host_dst [count][batch][row], through the handle's
+ * pinned staging buffer; returns after the copy landed.  Refuses slots beyond `recorded`. */
+int pl_mpc_log_read(pl_ocp* o, long long first_slot, long long count, double* host_dst);
+/* The device address of the log (for collectives; NULL with capacity 0); synchronises the
+ * handle's stream, as pl_mpc_export does. */
+int pl_mpc_log_device(pl_ocp* o, void** ptr);
+int pl_mpc_metrics(pl_ocp* o, pl_mpc_metrics_t* out /*[batch]*/);
+/* One problem's record step on the host, the code the device runs: the row of step k from
+ * x_init [nx], u0 [nu_0], stats, x_state [nx], ground_f [n_feet][3] (NULL: zeros), anchors
+ * [n_feet][3] (x, y, active; NULL: none) and the update of *metrics (the caller's, start values
+ * as above on a first step).  dz_tol, cz_min: one value each or NULL.  cursor [5] = {capacity,
+ * every, seen, recorded, dropped} of the caller's own log [capacity][row] (NULL with capacity 0):
+ * the row is written when the step gets a slot, and seen, recorded, dropped advance.  Works on a
+ * handle without a device. */
+int pl_mpc_record_host(const pl_ocp* o, int k, const double* x_init, const double* u0, const pl_stats* stats,
+                       const double* x_state, const double* ground_f, const double* anchors, double z_ref,
+                       const double* dz_tol, const double* cz_min, long long* cursor, double* log,
+                       pl_mpc_metrics_t* metrics);
+/* Pushes in step windows: while set, step k runs the plant with base wrench wrench[b] when
+ * k_start[b] <= k < k_end[b] and zero otherwise (PL_PLANT_ABA reads it, as the base_wrench of
+ * pl_mpc_set_disturbance).  k_start, k_end [batch], wrench [batch][6]; all NULL switches the
+ * schedule off and zeroes the wrench.  The window is applied by the gait / warm-start kernel,
+ * outside the captured step: no re-capture.  While a schedule is set, pl_mpc_set_disturbance
+ * with a base_wrench is refused (state noise is unaffected).  Refused before any device work:
+ * k_end < k_start, negative steps, non-finite wrench entries. */
+int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, const double* wrench);
+/* Steps k0 ... k0 + steps - 1, exactly a loop of pl_mpc_step: enqueued back to back, with no
+ * host synchronisation between them on the OSQP path.  A failing step ends the loop with its
+ * error. */
+int pl_mpc_run(pl_ocp* o, int k0, int steps);
 int pl_ocp_sync(pl_ocp* o);
 
 /* Host-side state maps, x = [q, v], dx = [dq, dv]

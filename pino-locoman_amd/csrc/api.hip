@@ -8,6 +8,7 @@
 // api_build.hip; the CasADi external-function ABI is api_casadi.hip.
 #include "api_internal.h"
 #include "plant.h"
+#include "record.h"
 #include "retract.h"
 
 #include <map>
@@ -430,6 +431,7 @@ extern "C" void pl_ocp_destroy(pl_ocp* o) {
     for (int k = 0; k < 5; ++k) hipEventDestroy(o->ev[k]);
     if (o->mpc_graph) hipGraphExecDestroy(o->mpc_graph);
     if (o->dl_host) hipHostFree(o->dl_host);
+    if (o->h.rec_log) hipFree(o->h.rec_log);
     if (o->rt_dev) hipFree(o->rt_dev);
     if (o->rt_host) hipHostFree(o->rt_host);
     hipStreamDestroy(o->h.stream);
@@ -1187,9 +1189,13 @@ extern "C" int pl_mpc_get_plant(const pl_ocp* o, int* mode, int* substeps) {
 extern "C" int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, const double* state_noise) {
   REQUIRE_DEVICE(o);
   PlOcpHandle* h = &o->h;
+  if (base_wrench && h->push_on) {  // one owner of d.plant_w
+    pl_set_error("pl_mpc_set_disturbance: a push schedule is set (pl_mpc_set_push) and owns the base wrench");
+    return -1;
+  }
   const size_t wb = (size_t)h->B * 6 * 8, nb = (size_t)h->B * h->ndx * 8;
   if (base_wrench) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_w, base_wrench, wb, hipMemcpyHostToDevice, h->stream));
-  else PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, wb, h->stream));  // k_plant always reads it: zero = none
+  else if (!h->push_on) PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, wb, h->stream));  // k_plant always reads it: zero = none
   if (state_noise) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_noise, state_noise, nb, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->plant_noise_on = state_noise ? 1 : 0;  // off: k_mpc_prepare's plain copy of x_state
@@ -1347,8 +1353,7 @@ extern "C" int pl_mpc_graph_info(const pl_ocp* o, long long* out) {
   return 0;
 }
 
-extern "C" int pl_mpc_step(pl_ocp* o, int k) {
-  REQUIRE_DEVICE(o);
+static int mpc_step_sequence(pl_ocp* o, int k) {
   // the event slots: 64 ADMM launches, 16 Hessian launches (an interior-point step makes <= 10)
   if (o->h.profile && (o->h.prof_n > 48 || o->h.prof_hn > 0)) prof_collect(&o->h);
   launch_mpc_prepare(&o->h, k);
@@ -1385,6 +1390,30 @@ extern "C" int pl_mpc_step(pl_ocp* o, int k) {
   return 0;
 }
 
+// The step's sequence, then, while the log is on, its record launch (k_record.hip): outside the
+// captured step, with the step index and the slot as plain arguments.
+extern "C" int pl_mpc_step(pl_ocp* o, int k) {
+  REQUIRE_DEVICE(o);
+  const int rc = mpc_step_sequence(o, k);
+  if (rc) return rc;
+  PlOcpHandle* h = &o->h;
+  if (h->rec_on) {
+    launch_mpc_record(h, k, pl::rec_slot(h->rec_capacity, h->rec_every, h->rec_cur), o->nodes[0].nu);
+    PL_CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+extern "C" int pl_mpc_run(pl_ocp* o, int k0, int steps) {
+  REQUIRE_DEVICE(o);
+  if (steps < 0) { pl_set_error("pl_mpc_run: steps %d is negative", steps); return -1; }
+  for (int k = k0; k < k0 + steps; ++k) {
+    const int rc = pl_mpc_step(o, k);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 extern "C" int pl_mpc_get_state(pl_ocp* o, double* x_state) {
   REQUIRE_DEVICE(o);
   PlOcpHandle* h = &o->h;
@@ -1413,19 +1442,24 @@ extern "C" int pl_mpc_export(pl_ocp* o, void* device_dst) {
   return 0;
 }
 
+// the handle's pinned staging buffer (pl_mpc_download, pl_mpc_log_read), grown on demand
+static int stage_reserve(pl_ocp* o, size_t bytes) {
+  if (o->dl_bytes >= bytes) return 0;
+  if (o->dl_host) hipHostFree(o->dl_host);
+  o->dl_host = nullptr;
+  o->dl_bytes = 0;
+  PL_CHECK_HIP(hipHostMalloc(&o->dl_host, bytes, hipHostMallocDefault));
+  o->dl_bytes = bytes;
+  return 0;
+}
+
 extern "C" int pl_mpc_download(pl_ocp* o, double* host_dst) {
   REQUIRE_DEVICE(o);
   if (!host_dst) { pl_set_error("null argument"); return -1; }
   PlOcpHandle* h = &o->h;
   const int nu0 = o->nodes[0].nu;
   const size_t row = (size_t)nu0 + h->nx, bytes = row * h->B * 8;
-  if (o->dl_bytes < bytes) {
-    if (o->dl_host) hipHostFree(o->dl_host);
-    o->dl_host = nullptr;
-    o->dl_bytes = 0;
-    PL_CHECK_HIP(hipHostMalloc(&o->dl_host, bytes, hipHostMallocDefault));
-    o->dl_bytes = bytes;
-  }
+  if (stage_reserve(o, bytes)) return -2;
   char* dst = (char*)o->dl_host;
   PL_CHECK_HIP(hipMemcpy2DAsync(dst, row * 8, h->d.x + h->ndx, (size_t)h->n * 8, (size_t)nu0 * 8, h->B,
                                 hipMemcpyDeviceToHost, h->stream));
@@ -1433,6 +1467,210 @@ extern "C" int pl_mpc_download(pl_ocp* o, double* host_dst) {
                                 h->B, hipMemcpyDeviceToHost, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   memcpy(host_dst, o->dl_host, bytes);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Rollout on the device (record.h, k_record.hip): the log of every step, the per-problem
+// metrics and the push schedule.  Their state sits behind the MPC graph key (state.h), and their
+// launches run outside the captured step.
+static_assert(sizeof(pl_mpc_metrics_t) == sizeof(PlMpcMetrics), "pl_mpc_metrics_t and PlMpcMetrics are one layout");
+static const double kNeverOut = 1.7976931348623157e308;  // |z - z_ref| > DBL_MAX, c_z < -DBL_MAX: never
+
+static int tol_check(const char* who, const char* name, const double* v, int count) {
+  for (int b = 0; v && b < count; ++b)
+    if (!std::isfinite(v[b])) {
+      pl_set_error("%s: problem %d: %s = %g is not finite", who, b, name, v[b]);
+      return -1;
+    }
+  return 0;
+}
+
+extern "C" int pl_mpc_log_start(pl_ocp* o, long long capacity, int every, const double* dz_tol, const double* cz_min) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (capacity < 0) { pl_set_error("pl_mpc_log_start: capacity %lld is negative", capacity); return -1; }
+  if (every < 1) { pl_set_error("pl_mpc_log_start: every = %d, must be at least 1", every); return -1; }
+  if (tol_check("pl_mpc_log_start", "dz_tol", dz_tol, o->h.B) || tol_check("pl_mpc_log_start", "cz_min", cz_min, o->h.B))
+    return -1;
+  PlOcpHandle* h = &o->h;
+  const size_t B = h->B;
+  const pl::RecLayout L = pl::rec_layout(h->nx, o->nodes[0].nu, h->oc.nfeet);
+  const size_t per_slot = B * (size_t)L.row;
+  if ((unsigned long long)capacity > (~(size_t)0 / sizeof(double)) / per_slot) {
+    pl_set_error("pl_mpc_log_start: capacity %lld x %zu doubles per slot does not fit an allocation", capacity, per_slot);
+    return -2;
+  }
+  REQUIRE_DEVICE(o);
+  h->rec_on = 0;
+  if (!h->rec_met && (dalloc(o, &h->rec_met, B) || dalloc(o, &h->rec_ref, 3 * B))) return -2;
+  const size_t need = (size_t)capacity * per_slot;
+  if (h->rec_log_doubles < need) {
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));  // an earlier record launch may still write the old log
+    if (h->rec_log) hipFree(h->rec_log);
+    h->rec_log = nullptr;
+    h->rec_log_doubles = 0;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, need * sizeof(double));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      pl_set_error("pl_mpc_log_start: hipMalloc(%zu bytes) for %lld slots: %s", need * sizeof(double), capacity,
+                   hipGetErrorString(e));
+      return -2;
+    }
+    h->rec_log = (double*)q;
+    h->rec_log_doubles = need;
+  }
+  std::vector<double> tol(2 * B);
+  for (size_t b = 0; b < B; ++b) {
+    tol[b] = dz_tol ? dz_tol[b] : kNeverOut;
+    tol[B + b] = cz_min ? cz_min[b] : -kNeverOut;
+  }
+  PL_CHECK_HIP(hipMemcpyAsync(h->rec_ref + B, tol.data(), 2 * B * 8, hipMemcpyHostToDevice, h->stream));
+  launch_mpc_record_start(h);  // metrics' start values, z_ref from x_state on the device
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));  // tol is read until the copy has run
+  h->rec_capacity = capacity;
+  h->rec_every = every;
+  h->rec_cur[0] = h->rec_cur[1] = h->rec_cur[2] = 0;
+  h->rec_on = 1;
+  return 0;
+}
+
+extern "C" int pl_mpc_log_stop(pl_ocp* o) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  o->h.rec_on = 0;
+  return 0;
+}
+
+extern "C" int pl_mpc_log_sizes(const pl_ocp* o, long long* out) {
+  if (!o || !out) { pl_set_error("null argument"); return -1; }
+  const PlOcpHandle& h = o->h;
+  const pl::RecLayout L = pl::rec_layout(h.nx, o->nodes[0].nu, h.oc.nfeet);
+  for (int f = 0; f < PL_REC_FIELDS; ++f) {
+    out[2 * f] = L.width[f];
+    out[2 * f + 1] = L.off[f];
+  }
+  out[12] = L.row;
+  out[13] = h.rec_capacity;
+  out[14] = h.rec_every;
+  out[15] = h.rec_cur[1];
+  out[16] = h.rec_cur[2];
+  return 0;
+}
+
+extern "C" int pl_mpc_log_read(pl_ocp* o, long long first_slot, long long count, double* host_dst) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (first_slot < 0 || count < 0 || first_slot > h->rec_cur[1] || count > h->rec_cur[1] - first_slot) {
+    pl_set_error("pl_mpc_log_read: slots [%lld, %lld + %lld) outside the %lld recorded", first_slot, first_slot, count,
+                 h->rec_cur[1]);
+    return -1;
+  }
+  if (count == 0) return 0;
+  if (!host_dst) { pl_set_error("null argument"); return -1; }
+  const pl::RecLayout L = pl::rec_layout(h->nx, o->nodes[0].nu, h->oc.nfeet);
+  const size_t per_slot = (size_t)h->B * L.row, bytes = (size_t)count * per_slot * 8;
+  if (stage_reserve(o, bytes)) return -2;
+  PL_CHECK_HIP(hipMemcpyAsync(o->dl_host, h->rec_log + (size_t)first_slot * per_slot, bytes, hipMemcpyDeviceToHost,
+                              h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  memcpy(host_dst, o->dl_host, bytes);
+  return 0;
+}
+
+extern "C" int pl_mpc_log_device(pl_ocp* o, void** ptr) {
+  REQUIRE_DEVICE(o);
+  if (!ptr) { pl_set_error("null argument"); return -1; }
+  PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
+  *ptr = o->h.rec_capacity > 0 ? o->h.rec_log : nullptr;
+  return 0;
+}
+
+extern "C" int pl_mpc_metrics(pl_ocp* o, pl_mpc_metrics_t* out) {
+  REQUIRE_DEVICE(o);
+  if (!out) { pl_set_error("null argument"); return -1; }
+  PlOcpHandle* h = &o->h;
+  if (!h->rec_met) { pl_set_error("pl_mpc_metrics: no log was started (pl_mpc_log_start)"); return -1; }
+  PL_CHECK_HIP(hipMemcpyAsync(out, h->rec_met, (size_t)h->B * sizeof(PlMpcMetrics), hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int pl_mpc_record_host(const pl_ocp* o, int k, const double* x_init, const double* u0, const pl_stats* stats,
+                                  const double* x_state, const double* ground_f, const double* anchors, double z_ref,
+                                  const double* dz_tol, const double* cz_min, long long* cursor, double* log,
+                                  pl_mpc_metrics_t* metrics) {
+  if (!o || !x_init || !u0 || !stats || !x_state || !cursor || !metrics) {
+    pl_set_error("pl_mpc_record_host: null argument");
+    return -1;
+  }
+  if (cursor[0] < 0 || cursor[1] < 1 || cursor[2] < 0 || cursor[3] < 0 || cursor[3] > cursor[0] || cursor[4] < 0) {
+    pl_set_error("pl_mpc_record_host: cursor {capacity %lld, every %lld, seen %lld, recorded %lld, dropped %lld} is not a log's",
+                 cursor[0], cursor[1], cursor[2], cursor[3], cursor[4]);
+    return -1;
+  }
+  if (cursor[0] > 0 && !log) { pl_set_error("pl_mpc_record_host: capacity %lld without a log", cursor[0]); return -1; }
+  if (tol_check("pl_mpc_record_host", "dz_tol", dz_tol, 1) || tol_check("pl_mpc_record_host", "cz_min", cz_min, 1))
+    return -1;
+  const PlOcpHandle& h = o->h;
+  // pl_stats back into the kernel's PlProbInfo (fetch_stats is the other direction)
+  PlProbInfo info;
+  memset(&info, 0, sizeof(info));
+  info.status = stats->status;
+  info.iter = stats->admm_iters;
+  info.ls_accepted = stats->ls_accepted;
+  info.ls_alpha = stats->ls_alpha;
+  info.viol_max = stats->viol_max;
+  info.pri_res = stats->pri_res;
+  info.dua_res = stats->dua_res;
+  info.f = stats->f;
+  const double zero[3 * PL_MAXFEET] = {0.0};
+  const pl::RecSrc S{x_init, u0, &info, x_state, ground_f ? ground_f : zero, anchors ? anchors : zero};
+  PlMpcMetrics m;
+  memcpy(&m, metrics, sizeof(m));
+  pl::record_host(h.nx, o->nodes[0].nu, h.oc.nfeet, PL_IS_CV(h.oc.dyn) ? 6 : 0, k, S, z_ref,
+                  dz_tol ? *dz_tol : kNeverOut, cz_min ? *cz_min : -kNeverOut, cursor[0], cursor[1], cursor + 2, log, &m);
+  memcpy(metrics, &m, sizeof(m));
+  return 0;
+}
+
+extern "C" int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, const double* wrench) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  const bool off = !k_start && !k_end && !wrench;
+  if (!off && (!k_start || !k_end || !wrench)) {
+    pl_set_error("pl_mpc_set_push: k_start, k_end and wrench go together (all NULL switches the schedule off)");
+    return -1;
+  }
+  const size_t B = o->h.B;
+  for (size_t b = 0; !off && b < B; ++b) {
+    if (k_start[b] < 0 || k_end[b] < 0) {
+      pl_set_error("pl_mpc_set_push: problem %zu: window [%d, %d) has a negative step", b, k_start[b], k_end[b]);
+      return -1;
+    }
+    if (k_end[b] < k_start[b]) {
+      pl_set_error("pl_mpc_set_push: problem %zu: window [%d, %d) ends before it starts", b, k_start[b], k_end[b]);
+      return -1;
+    }
+    for (int j = 0; j < 6; ++j)
+      if (!std::isfinite(wrench[6 * b + j])) {
+        pl_set_error("pl_mpc_set_push: problem %zu: wrench[%d] = %g is not finite", b, j, wrench[6 * b + j]);
+        return -1;
+      }
+  }
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (off) {
+    h->push_on = 0;
+    PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, B * 6 * 8, h->stream));
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  }
+  if (!h->push_k && (dalloc(o, &h->push_k, 2 * B) || dalloc(o, &h->push_w, 6 * B))) return -2;
+  PL_CHECK_HIP(hipMemcpyAsync(h->push_k, k_start, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipMemcpyAsync(h->push_k + B, k_end, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipMemcpyAsync(h->push_w, wrench, B * 6 * 8, hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  h->push_on = 1;
   return 0;
 }
 

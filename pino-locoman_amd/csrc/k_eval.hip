@@ -414,11 +414,18 @@ void launch_line_search(PlOcpHandle* h) {
 // x_init = state_integrate(x_state, noise_b), the "add noise to x_init" of run_mpc.py:79-82;
 // x_state stays the true state.
 __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n, int np, int nx, int gait_type,
-                                                    double period, double swing_period, const double* noise) {
+                                                    double period, double swing_period, const double* noise,
+                                                    const int* push_k, const double* push_w) {
   const int b = blockIdx.x;
   const PlOcpConst& O = *d.oc;
   const PlModel& M = *d.model;
   double* p = d.p + (size_t)b * np;
+  // push schedule (pl_mpc_set_push, null: none): the plant's base wrench of this step is the
+  // problem's wrench inside its window [k_start, k_end) and zero outside; k_plant reads it as ever
+  if (push_k && threadIdx.x < 6) {
+    const bool in = push_k[b] <= k && k < push_k[gridDim.x + b];
+    d.plant_w[(size_t)b * 6 + threadIdx.x] = in ? push_w[(size_t)b * 6 + threadIdx.x] : 0.0;
+  }
   if (!noise) {
     for (int j = threadIdx.x; j < nx; j += blockDim.x) p[O.P.x_init + j] = d.xstate[(size_t)b * nx + j];
   } else if (threadIdx.x == 0) {
@@ -478,7 +485,8 @@ __global__ void k_mpc_finish(PlDev d, int B, int n, int nx) {
 void launch_mpc_prepare(PlOcpHandle* h, int k) {
   hipLaunchKernelGGL(k_mpc_prepare, dim3(h->B), dim3(64), 0, h->stream, h->d, k, h->N, h->n, h->np, h->nx,
                      h->gait_type, h->gait_period, h->swing_period,
-                     h->plant_noise_on ? (const double*)h->d.plant_noise : nullptr);
+                     h->plant_noise_on ? (const double*)h->d.plant_noise : nullptr,
+                     h->push_on ? (const int*)h->push_k : nullptr, (const double*)h->push_w);
 }
 
 void launch_mpc_finish(PlOcpHandle* h) {

@@ -378,6 +378,19 @@ struct PlOcpHandle {
   int prof_hn;
   double prof_hess_ms;
   long long prof_hess_launches;
+  // Rollout log and push schedule (record.h, k_record.hip), outside the key as well: their
+  // launches (k_mpc_record, k_mpc_prepare) run outside the captured step and take these as plain
+  // arguments, so starting, stopping or re-sizing the log and setting a schedule never re-capture.
+  int rec_on;                  // 1 between pl_mpc_log_start and pl_mpc_log_stop: pl_mpc_step launches k_mpc_record
+  long long rec_capacity, rec_every;
+  long long rec_cur[3];        // steps seen since the start, slots recorded, steps dropped (pl::rec_slot)
+  double* rec_log;             // [capacity][B][row], the handle's own allocation (grown by pl_mpc_log_start)
+  size_t rec_log_doubles;      // its size
+  struct PlMpcMetrics* rec_met;  // [B]
+  double* rec_ref;             // [3][B]: z_ref, dz_tol, cz_min
+  int push_on;                 // 1 while pl_mpc_set_push holds a schedule: k_mpc_prepare writes d.plant_w
+  int* push_k;                 // [2][B]: k_start, k_end
+  double* push_w;              // [B][6]
 };
 
 // ---- kernel launchers (defined in the k_*.hip translation units)
@@ -409,6 +422,8 @@ void launch_line_search(PlOcpHandle* h);
 void launch_mpc_prepare(PlOcpHandle* h, int k);
 void launch_mpc_finish(PlOcpHandle* h);
 void launch_plant(PlOcpHandle* h);  // k_plant.hip
+void launch_mpc_record(PlOcpHandle* h, int k, long long slot, int nu0);  // k_record.hip
+void launch_mpc_record_start(PlOcpHandle* h);
 void launch_retract(PlOcpHandle* h, int steps, int terminal, double* out);  // k_retract.hip
 void launch_reset_info(PlOcpHandle* h);
 void launch_reset_iterates(PlOcpHandle* h);

@@ -69,6 +69,14 @@ class ContactParams(C.Structure):
                 ("mu", C.c_double), ("kp", C.c_double), ("kd", C.c_double), ("pad", C.c_double)]
 
 
+class MpcMetrics(C.Structure):
+    _fields_ = [("steps", C.c_int), ("first_nonfinite", C.c_int), ("first_out", C.c_int),
+                ("n_not_solved", C.c_int), ("n_ls_rejected", C.c_int), ("pad", C.c_int),
+                ("max_dz", C.c_double), ("min_cz", C.c_double), ("max_viol", C.c_double)]
+
+
+_llp = C.POINTER(C.c_longlong)
+
 EXPORTS = {
     "pl_last_error": (C.c_char_p, []),
     "pl_version": (C.c_int, []),
@@ -123,6 +131,16 @@ EXPORTS = {
     "pl_ocp_profile_read_hess": (C.c_int, [C.c_void_p, _dp]),
     "pl_mpc_graph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "pl_mpc_set_ip_lam": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl_mpc_log_start": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, _dp, _dp]),
+    "pl_mpc_log_stop": (C.c_int, [C.c_void_p]),
+    "pl_mpc_log_sizes": (C.c_int, [C.c_void_p, _llp]),
+    "pl_mpc_log_read": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, _dp]),
+    "pl_mpc_log_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pl_mpc_metrics": (C.c_int, [C.c_void_p, C.POINTER(MpcMetrics)]),
+    "pl_mpc_record_host": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(Stats), _dp, _dp, _dp, C.c_double,
+                                     _dp, _dp, _llp, _dp, C.POINTER(MpcMetrics)]),
+    "pl_mpc_set_push": (C.c_int, [C.c_void_p, _ip, _ip, _dp]),
+    "pl_mpc_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_ocp_sync": (C.c_int, [C.c_void_p]),
     "pl_state_integrate": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "pl_state_difference": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),

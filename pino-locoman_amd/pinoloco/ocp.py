@@ -580,6 +580,116 @@ class BatchedOCP:
         _lib.check(_lib.lib().pl_mpc_download(self.h, _lib.dptr(out)))
         return out
 
+    # ---------------------------------------------------------------- rollout on the device
+    LOG_FIELDS = ("x_init", "u0", "stats", "x_state", "ground_f", "anchor_active")
+    LOG_STATS = ("status", "admm_iters", "ls_accepted", "ls_alpha", "viol_max", "f", "pri_res", "dua_res")
+    METRIC_FIELDS = tuple(k for k, _ in _lib.MpcMetrics._fields_ if k != "pad")
+
+    def _per_problem(self, a, name, count=None, dtype=np.float64, width=None):
+        """None, or a contiguous [count] ([count][width]) array from a scalar or an array."""
+        if a is None:
+            return None
+        count = self.batch if count is None else count
+        shape = (count,) if width is None else (count, width)
+        a = np.asarray(a, dtype=dtype)
+        if a.shape not in ((), shape):
+            raise _lib.PinolocoError(f"{name} has shape {a.shape}, expected a scalar or {shape}")
+        return np.ascontiguousarray(np.broadcast_to(a, shape))
+
+    def mpc_log_sizes(self):
+        """Layout of a log row: per field of LOG_FIELDS its ``width`` and ``offset`` (doubles), and
+        ``row``, ``capacity``, ``every``, ``recorded``, ``dropped``.  The field sizes need no device."""
+        out = (C.c_longlong * 17)()
+        _lib.check(_lib.lib().pl_mpc_log_sizes(self.h, out))
+        sz = {f: {"width": int(out[2 * k]), "offset": int(out[2 * k + 1])} for k, f in enumerate(self.LOG_FIELDS)}
+        sz.update(row=int(out[12]), capacity=int(out[13]), every=int(out[14]), recorded=int(out[15]),
+                  dropped=int(out[16]))
+        return sz
+
+    def mpc_log_start(self, capacity=0, every=1, dz_tol=None, cz_min=None):
+        """Start the rollout log (pl_mpc_log_start), after mpc_setup: from now on every mpc_step
+        also records a row on the device (every ``every``-th step, into ``capacity`` slots; further
+        steps are counted as dropped) and updates the per-problem metrics; capacity 0 keeps the
+        metrics only.  dz_tol / cz_min: a scalar or [batch], None = never out by that test."""
+        dz = self._per_problem(dz_tol, "dz_tol")
+        cz = self._per_problem(cz_min, "cz_min")
+        _lib.check(_lib.lib().pl_mpc_log_start(self.h, int(capacity), int(every), None if dz is None else _lib.dptr(dz),
+                                               None if cz is None else _lib.dptr(cz)))
+
+    def mpc_log_stop(self):
+        """Stop recording; the log and the metrics stay readable."""
+        _lib.check(_lib.lib().pl_mpc_log_stop(self.h))
+
+    def _split_rows(self, rows, sz):
+        return {f: rows[..., sz[f]["offset"]:sz[f]["offset"] + sz[f]["width"]] for f in self.LOG_FIELDS}
+
+    def mpc_log_read(self, first=0, count=None):
+        """The recorded rows as a dict of arrays, one per field of LOG_FIELDS, each
+        [recorded][batch][width] (views of one array); stats columns are LOG_STATS."""
+        sz = self.mpc_log_sizes()
+        count = sz["recorded"] - first if count is None else int(count)
+        rows = np.zeros((max(count, 0), self.batch, sz["row"]))
+        _lib.check(_lib.lib().pl_mpc_log_read(self.h, int(first), count, _lib.dptr(rows)))
+        return self._split_rows(rows, sz)
+
+    def mpc_log_device(self):
+        """Device address of the log ([capacity][batch][row] doubles; None with capacity 0), after a
+        synchronise of the handle's stream."""
+        p = C.c_void_p()
+        _lib.check(_lib.lib().pl_mpc_log_device(self.h, C.byref(p)))
+        return p.value
+
+    def mpc_metrics(self):
+        """The per-problem outcome so far: a dict of [batch] arrays, one per field of METRIC_FIELDS."""
+        m = (_lib.MpcMetrics * self.batch)()
+        _lib.check(_lib.lib().pl_mpc_metrics(self.h, m))
+        return {k: np.array([getattr(s, k) for s in m]) for k in self.METRIC_FIELDS}
+
+    def mpc_set_push(self, k_start=None, k_end=None, wrench=None):
+        """Pushes in step windows (pl_mpc_set_push): step k runs the "aba" plant with base wrench
+        wrench[b] when k_start[b] <= k < k_end[b], zero otherwise.  k_start, k_end: a scalar or
+        [batch]; wrench [batch][6].  All None switches the schedule off."""
+        k0 = self._per_problem(k_start, "k_start", dtype=np.int32)
+        k1 = self._per_problem(k_end, "k_end", dtype=np.int32)
+        w = self._per_problem(wrench, "wrench", width=6)
+        _lib.check(_lib.lib().pl_mpc_set_push(self.h, None if k0 is None else _lib.iptr(k0),
+                                              None if k1 is None else _lib.iptr(k1),
+                                              None if w is None else _lib.dptr(w)))
+
+    def mpc_run(self, k0, steps):
+        """mpc_step(k0) ... mpc_step(k0 + steps - 1), enqueued back to back (pl_mpc_run)."""
+        _lib.check(_lib.lib().pl_mpc_run(self.h, int(k0), int(steps)))
+
+    def mpc_record_host(self, steps, z_ref, capacity=0, every=1, dz_tol=None, cz_min=None):
+        """One problem's record steps on the host, the code the device runs (pl_mpc_record_host).
+        steps: a list of dicts with k, x_init [nx], u0 [nu_0], stats (a dict of LOG_STATS), x_state
+        [nx] and optionally ground_f [n_feet][3], anchors [n_feet][3].  Returns (log, metrics,
+        cursor): the rows as mpc_log_read returns them, without the batch axis; the metrics as a
+        dict of scalars; cursor with seen, recorded, dropped.  Needs no device."""
+        sz = self.mpc_log_sizes()
+        nx, nu0 = sz["x_init"]["width"], sz["u0"]["width"]
+        log = np.zeros((max(int(capacity), 0), sz["row"]))
+        cur = (C.c_longlong * 5)(int(capacity), int(every), 0, 0, 0)
+        m = _lib.MpcMetrics(0, -1, -1, 0, 0, 0, 0.0, 1.0, 0.0)
+        dz = self._per_problem(dz_tol, "dz_tol", 1)
+        cz = self._per_problem(cz_min, "cz_min", 1)
+        for s in steps:
+            xi = self._per_problem(s["x_init"], "x_init", nx)
+            u0 = self._per_problem(s["u0"], "u0", nu0)
+            xs = self._per_problem(s["x_state"], "x_state", nx)
+            gf = self._per_problem(s.get("ground_f"), "ground_f", self.N_FEET, width=3)
+            an = self._per_problem(s.get("anchors"), "anchors", self.N_FEET, width=3)
+            st = _lib.Stats()
+            for name in self.LOG_STATS:
+                setattr(st, name, type(getattr(st, name))(s["stats"][name]))
+            _lib.check(_lib.lib().pl_mpc_record_host(
+                self.h, int(s["k"]), _lib.dptr(xi), _lib.dptr(u0), C.byref(st), _lib.dptr(xs),
+                None if gf is None else _lib.dptr(gf), None if an is None else _lib.dptr(an), float(z_ref),
+                None if dz is None else _lib.dptr(dz), None if cz is None else _lib.dptr(cz), cur,
+                _lib.dptr(log) if log.size else None, C.byref(m)))
+        return (self._split_rows(log[:cur[3]], sz), {k: getattr(m, k) for k in self.METRIC_FIELDS},
+                {"seen": int(cur[2]), "recorded": int(cur[3]), "dropped": int(cur[4])})
+
     # ---------------------------------------------------------------- retract
     RETRACT_FIELDS = ("q", "v", "a", "forces", "tau", "eom_base")
 

@@ -9,11 +9,18 @@ Two runs, one problem per value:
 Per problem: whether the state stayed finite and the base within 10 cm of its starting height over
 the whole run, and the largest height deviation.  Writes profiles/plant/contact_demo.json (--out).
 Nothing here is a pass bar: it records what the loop does on this ground.
+
+The rollout runs on the device: the push is a window of mpc_set_push, the outcome comes from the
+metrics of mpc_log_start(capacity=0) (dz_tol = 10 cm), and mpc_run enqueues all steps; the host
+reads the metrics once at the end.  --stepwise is the loop driven from the host instead: per step
+mpc_step, a blocking mpc_state(), the outcome in numpy, the push switched by mpc_set_disturbance.
+"wall_s" is the loop's wall time (first step enqueued to outcome on the host) in either mode.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -46,22 +53,37 @@ def run(kind, args):
     bo.mpc_set_contact(c, bo.ground_under_feet(x0, 0.005))
     W = np.zeros((B, 6))
     W[:, 1] = args.push_max * ramp
-    finite, dz = np.ones(B, bool), np.zeros(B)
-    for k in range(args.steps):
-        if kind == "push" and k == 50:
-            bo.mpc_set_disturbance(base_wrench=W)
-        if kind == "push" and k == 60:
-            bo.mpc_set_disturbance()
-        bo.mpc_step(k)
+    bo.sync()
+    t_start = time.perf_counter()
+    if args.stepwise:
+        finite, dz = np.ones(B, bool), np.zeros(B)
+        for k in range(args.steps):
+            if kind == "push" and k == 50:
+                bo.mpc_set_disturbance(base_wrench=W)
+            if kind == "push" and k == 60:
+                bo.mpc_set_disturbance()
+            bo.mpc_step(k)
+            xs = bo.mpc_state()
+            ok = np.all(np.isfinite(xs), axis=1)
+            finite &= ok
+            dz = np.where(ok, np.maximum(dz, np.abs(xs[:, 2] - x0[2])), dz)
+        up = finite & (dz < 0.10)
+    else:
+        if kind == "push":
+            bo.mpc_set_push(50, 60, W)
+        # out = more than 10 cm from the starting height; "within" is dz < 0.10, so a deviation of
+        # exactly the tolerance counts as out here as well: max_dz decides, not first_out
+        bo.mpc_log_start(capacity=0, dz_tol=0.10)
+        bo.mpc_run(0, args.steps)
+        m = bo.mpc_metrics()
+        finite, dz = m["first_nonfinite"] < 0, m["max_dz"]
+        up = finite & (dz < 0.10)
         xs = bo.mpc_state()
-        ok = np.all(np.isfinite(xs), axis=1)
-        finite &= ok
-        dz = np.where(ok, np.maximum(dz, np.abs(xs[:, 2] - x0[2])), dz)
+    wall = time.perf_counter() - t_start
     feet = bo.mpc_get_contact()["anchors"][:, :, 2].sum(1)
     status = bo.mpc_stats()["status"]
     bo.close()
-    up = finite & (dz < 0.10)
-    return {"value": (W[:, 1] if kind == "push" else c["mu"]).tolist(), "finite": finite.tolist(),
+    return {"value": (W[:, 1] if kind == "push" else c["mu"]).tolist(), "wall_s": wall, "finite": finite.tolist(),
             "within_10cm": up.tolist(), "max_height_dev": dz.tolist(), "feet_on_ground_at_end": feet.tolist(),
             "final_xy": xs[:, :2].tolist(), "solver_status_at_end": status.tolist(),
             "survived": int(up.sum()), "of": B}
@@ -75,12 +97,13 @@ ap.add_argument("--substeps", type=int, default=16)
 ap.add_argument("--kp", type=float, default=40.0)
 ap.add_argument("--kd", type=float, default=1.0)
 ap.add_argument("--push-max", type=float, default=100.0)
+ap.add_argument("--stepwise", action="store_true", help="drive the loop from the host, one blocking read per step")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plant", "contact_demo.json"))
 a = ap.parse_args()
-res = {"setup": {k: getattr(a, k) for k in ("batch", "nodes", "steps", "substeps", "kp", "kd", "push_max")}}
+res = {"setup": {k: getattr(a, k) for k in ("batch", "nodes", "steps", "substeps", "kp", "kd", "push_max", "stepwise")}}
 for kind in ("push", "mu"):
     res[kind] = run(kind, a)
-    print(kind, "survived", res[kind]["survived"], "of", res[kind]["of"], flush=True)
+    print(kind, "survived", res[kind]["survived"], "of", res[kind]["of"], f"in {res[kind]['wall_s']:.2f} s", flush=True)
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 with open(a.out, "w") as f:
     f.write(json.dumps(res, indent=1) + "\n")

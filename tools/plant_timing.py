@@ -7,10 +7,14 @@ Two halves, because a kernel's own time comes from the profiler's kernel trace, 
       an MPC loop (3 warm-up steps + 10) with the plant as given; eager launches (no_mpc_graph), so
       every launch is one dispatch of the trace.  The plant runs on the solved iterate of each step.
       --contact adds the ground contact and joint PD of mpc_set_contact (k_plant's contact
-      instantiation; profiles/plant/plant_contact_timing.json).
-  python tools/plant_timing.py parse LABEL=DIR [LABEL=DIR ...] [--out FILE]
+      instantiation; profiles/plant/plant_contact_timing.json).  --log switches the rollout log on
+      (mpc_log_start, one slot per step), so that every step also dispatches k_mpc_record
+      (profiles/plant/record_timing.json).
+  python tools/plant_timing.py parse LABEL[@KERNEL]=DIR [LABEL[@KERNEL]=DIR ...] [--out FILE]
       per label the median / min / max duration of the last 10 k_plant or k_mpc_finish dispatches
-      of DIR's *kernel_trace.csv, as one JSON.
+      of DIR's *kernel_trace.csv, as one JSON; @KERNEL picks the dispatches whose name contains
+      KERNEL instead ("k_mpc_record(" and k_mpc_finish of one --log run; the bracket keeps
+      k_mpc_record_start, the one launch of mpc_log_start, out).
 
 The PINOLOCO_LIB environment variable selects another build of the library (e.g. one built with
 PL_HIPCC_DEFS=-DPL_PLANT_LANES=64) for a same-box comparison of the mapping.
@@ -53,11 +57,18 @@ def run(args):
         # does not depend on the values.
         c = bo.contact_defaults(penetration=args.penetration, zeta=args.zeta, kp=40.0, kd=1.0)
         bo.mpc_set_contact(c, bo.ground_under_feet(XS, args.penetration))
+    if args.log:
+        bo.mpc_log_start(capacity=WARM + STEPS, dz_tol=0.1, cz_min=0.5)
     for k in range(WARM + STEPS):
         bo.mpc_step(k)
     xs = bo.mpc_state()
     out = {"mode": args.mode, "substeps": args.substeps, "contact": bool(args.contact), "shape": args.shape,
            "lib": _lib.LIB_PATH, "lib_src_sha256": _lib.build_sha(), "finite": bool(np.all(np.isfinite(xs)))}
+    if args.log:
+        sz = bo.mpc_log_sizes()
+        out["log"] = {k: sz[k] for k in ("row", "recorded", "dropped")}
+        out["log_last_state_is_state"] = bool(np.array_equal(bo.mpc_log_read(WARM + STEPS - 1, 1)["x_state"][0], xs,
+                                                            equal_nan=True))
     if args.contact:
         out["feet_on_ground"] = float(bo.mpc_get_contact()["anchors"][:, :, 2].mean())
     print(json.dumps(out))
@@ -68,6 +79,7 @@ def parse(args):
     out = {}
     for item in args.dirs:
         label, d = item.split("=", 1)
+        label, _, pick = label.partition("@")
         files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
         if len(files) != 1:
             raise SystemExit(f"{label}: expected one kernel trace under {d}, found {files}")
@@ -75,7 +87,7 @@ def parse(args):
         with open(files[0]) as f:
             for row in csv.DictReader(f):
                 kn = row["Kernel_Name"]
-                if "k_plant" in kn or "k_mpc_finish" in kn:
+                if (pick in kn) if pick else ("k_plant" in kn or "k_mpc_finish" in kn):
                     name = kn
                     ns.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"]),
                                int(row["Workgroup_Size_X"]), int(row["Grid_Size_X"]), int(row["Scratch_Size"])))
@@ -99,6 +111,7 @@ r = sub.add_parser("run")
 r.add_argument("--mode", default="aba", choices=["aba", "nominal"])
 r.add_argument("--substeps", type=int, default=1)
 r.add_argument("--contact", action="store_true", help="ground contact and joint PD (mpc_set_contact), aba only")
+r.add_argument("--log", action="store_true", help="the rollout log on: k_mpc_record after every step")
 r.add_argument("--penetration", type=float, default=0.05)
 r.add_argument("--zeta", type=float, default=0.05)
 r.add_argument("shape", nargs="*", default=["b2g", "whole_body_rnea", "50", "1024"])
