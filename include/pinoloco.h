@@ -538,7 +538,14 @@ int pl_debug_get(pl_ocp* o, const char* name, double* out, long long count);
 int pl_debug_set(pl_ocp* o, const char* name, const double* in, long long count);
 int pl_debug_nodes(const pl_ocp* o, int* out);
 int pl_debug_consts(const pl_ocp* o, void* model_out, void* oc_out, int* sizes);
+/* reset bit 0: start from x = z = y = 0; bit 1: the last iteration stores delta x / delta y
+ * ("dxs", "dys") as a check iteration of pl_ocp_solve does. */
 int pl_debug_admm(pl_ocp* o, int niter, int reset);
+/* Ruiz scaling + scaled data alone on the raw arrays as they are (no evaluation, no factor). */
+int pl_debug_qp_setup(pl_ocp* o);
+/* One termination check on the current iterates and scaled data, then (unscale) the step
+ * write-back; read status / pri_res / dua_res with pl_mpc_get_stats. */
+int pl_debug_check(pl_ocp* o, int final_check, int unscale);
 
 #ifdef __cplusplus
 }

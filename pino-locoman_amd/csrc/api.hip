@@ -1879,6 +1879,9 @@ static int debug_rw(pl_ocp* o, const char* name, double* out, const double* in, 
       {"FS", h->d.FS, h->d.FS ? B * (size_t)h->fs_stride : 0},
       {"rhs", h->d.rhs, B * h->n}, {"step", h->d.step, B * h->n},   {"grad", h->d.grad, B * h->n},
       {"g", h->d.g, B * h->m},     {"xstate", h->d.xstate, B * h->nx},
+      {"dxs", h->d.dxs, B * h->n}, {"dys", h->d.dys, B * h->m},     {"chk", h->d.chk, B * (size_t)(h->N + 1) * 8},
+      {"lbg", h->d.lbg, B * h->m}, {"ubg", h->d.ubg, B * h->m},
+      {"rhoc", h->d.rhoc, B * (size_t)(h->N + 1) * std::max(h->ncpl_max, 1)},
       {"ip_s", h->d.ip_s, h->d.ip_s ? B * h->m : 0},     {"ip_lam", h->d.ip_lam, h->d.ip_lam ? B * h->m : 0},
       {"ip_lam0", h->d.ip_lam0, h->d.ip_lam0 ? B * h->m : 0},
       {"ip_zl", h->d.ip_zl, h->d.ip_zl ? B * h->m : 0},  {"ip_zu", h->d.ip_zu, h->d.ip_zu ? B * h->m : 0},
@@ -1963,7 +1966,9 @@ extern "C" int pl_debug_consts(const pl_ocp* o, void* model_out, void* oc_out, i
 }
 
 // Tests: evaluate + scale + factor, then exactly `niter` ADMM iterations from the
-// current iterates (no termination checks, no line search).
+// current iterates (no termination checks, no line search).  reset bit 0: from x = z = y = 0;
+// bit 1: the last iteration stores delta x / delta y (d.dxs, d.dys) as a check iteration of
+// pl_ocp_solve does.
 extern "C" int pl_debug_admm(pl_ocp* o, int niter, int reset) {
   REQUIRE_DEVICE(o);
   PlOcpHandle* h = &o->h;
@@ -1973,9 +1978,34 @@ extern "C" int pl_debug_admm(pl_ocp* o, int niter, int reset) {
   launch_qp_setup(h);
   launch_factor(h);
   launch_reset_info(h);
-  if (reset) launch_reset_iterates(h);
+  if (reset & 1) launch_reset_iterates(h);
   launch_admm_init(h);
-  if (niter > 0) launch_admm(h, niter, 0, 0);
+  if (niter > 0) launch_admm(h, niter, (reset & 2) ? 1 : 0, 0);
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Tests: Ruiz scaling and k_qp_finish alone on whatever Araw, P, grad, g, lbg, ubg hold now
+// (no evaluation, so pl_debug_set can overwrite the raw data first; no factor).
+extern "C" int pl_debug_qp_setup(pl_ocp* o) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  launch_qp_setup(h);
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Tests: one termination check (k_check_part, k_check) on the current xa, za, ya, dxs, dys
+// and scaled data, then k_unscale if asked; status, pri_res and dua_res come back through
+// pl_mpc_get_stats.  Does not evaluate, scale or factor.
+extern "C" int pl_debug_check(pl_ocp* o, int final_check, int unscale) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  launch_reset_info(h);
+  launch_check(h, 0, final_check ? 1 : 0);
+  if (unscale) launch_unscale(h);
   PL_CHECK_HIP(hipGetLastError());
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   return 0;

@@ -152,6 +152,8 @@ EXPORTS = {
     "pl_debug_set": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_longlong]),
     "pl_debug_nodes": (C.c_int, [C.c_void_p, _ip]),
     "pl_debug_admm": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pl_debug_qp_setup": (C.c_int, [C.c_void_p]),
+    "pl_debug_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_dyn_create": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pl_dyn_destroy": (None, [C.c_void_p]),
     "pl_dyn_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip]),

@@ -398,13 +398,27 @@ class BatchedOCP:
         v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
         _lib.check(_lib.lib().pl_debug_set(self.h, name.encode(), _lib.dptr(v), v.size))
 
-    def debug_admm(self, niter, reset=True):
+    def debug_admm(self, niter, reset=True, delta=False):
         """Stage tests: evaluate, scale and factor at the current x, then exactly ``niter`` ADMM
         iterations of the selected kernel with no termination check and no line search
-        (reset: from x = z = y = 0, else from the iterates on the device).  debug("xa" | "za" |
+        (reset: from x = z = y = 0, else from the iterates on the device; delta: the last
+        iteration stores "dxs" / "dys" as a check iteration of solve() does).  debug("xa" | "za" |
         "ya" | "As" | "Ps" | "qs" | "ls" | "us" | "rho" | "S" | "FS", ...) then read the scaled
         iterates and data.  Call after set_params, set_x and init_solver."""
-        _lib.check(_lib.lib().pl_debug_admm(self.h, int(niter), int(bool(reset))))
+        _lib.check(_lib.lib().pl_debug_admm(self.h, int(niter), int(bool(reset)) | (2 if delta else 0)))
+
+    def debug_qp_setup(self):
+        """Stage tests: Ruiz scaling and the scaled data (D, E, cs, As, Ps, qs, ls, us, rho,
+        rhoc) from the raw arrays as they are on the device ("Araw", "P", "grad", "g", "lbg",
+        "ubg", which debug_set may have overwritten); no evaluation and no factor."""
+        _lib.check(_lib.lib().pl_debug_qp_setup(self.h))
+
+    def debug_check(self, final=False, unscale=False):
+        """Stage tests: one termination check on the device's current iterates, deltas and
+        scaled data (final: with the x10 pass and MAX_ITER), then the step write-back if
+        ``unscale``; returns mpc_stats() (status, pri_res, dua_res)."""
+        _lib.check(_lib.lib().pl_debug_check(self.h, int(bool(final)), int(bool(unscale))))
+        return self.mpc_stats()
 
     def lag_hess(self):
         """The interior point's Lagrangian Hessian blocks of the last Newton system (tests):
