@@ -490,6 +490,36 @@ int pl_dyn_sizes(const pl_dyn* d, int fn, int flags, int* in_len, int* out_len);
 int pl_dyn_eval(pl_dyn* d, int fn, int batch, int frame, int flags, const double* in0, const double* in1,
                 const double* in2, const double* in3, double* out);
 
+/* Jacobian of a point function with respect to its inputs, in tangent coordinates (the role of
+ * ca.jacobian of the reference's point functions, optimization/ocp.py:283-284).
+ *   wrt      bit k selects input k; W = sum of tan_len[k] over the selected inputs; the columns of
+ *            jac are the selected inputs' tangents in input order.
+ *   jac      caller-owned [batch][out_len][W] float64, row-major per point.
+ *   tangent  an input that is a configuration q (length nq: in1 of PL_FN_BASE_VEL_CV and
+ *            PL_FN_GAPS_CV, in0 of every other supported function) has tan_len = nv: column k is
+ *            d/d eps f(integrate(q, eps e_k)) at eps = 0, integrate = pinocchio's (local free-flyer
+ *            twist, linear then angular; revolute coordinates add) -- the convention of
+ *            computeRNEADerivatives and of the OCP's own dq columns.  Every other input is
+ *            Euclidean: tan_len = in_len.
+ *   out      optional [batch][out_len]: the value by the plain double path, bit-identical to
+ *            pl_dyn_eval.
+ *   supported  PL_FN_RNEA, _ABA, _FRAME_POS, _FRAME_VEL (flags bit 1 as in pl_dyn_eval), _GAPS_WB,
+ *            _BASE_ACC_WB, _COM_DYN, _BASE_VEL_CV, _BASE_ACC_CV, _GAPS_CV, _NLE, _COM, _GAPS_CA,
+ *            each with flags bit 0 as pl_dyn_eval takes it.
+ *   refused  (message in pl_last_error names the function) the matrix-valued PL_FN_CRBA,
+ *            _FRAME_JAC, _CMAP; the state maps PL_FN_INTEGRATE_* / _DIFFERENCE_* (their outputs or
+ *            branch points live on the manifold, and the OCP rows are linear in dx); wrt == 0; a wrt
+ *            bit on an input the function does not take; a missing input; jac == NULL; everything
+ *            pl_dyn_eval refuses.  batch == 0 returns 0.
+ * pl_dyn_jac_sizes: in_len[4], tan_len[4] (0 for an absent input) and out_len of one point. */
+int pl_dyn_jac_sizes(const pl_dyn* d, int fn, int flags, int* in_len, int* tan_len, int* out_len);
+int pl_dyn_jac(pl_dyn* d, int fn, int batch, int frame, int flags, unsigned wrt, const double* in0,
+               const double* in1, const double* in2, const double* in3, double* out, double* jac);
+/* The same with every pointer a DEVICE pointer on the handle's device (refused on a device = -1
+ * handle); synchronises the handle's stream before returning, as pl_mpc_export does. */
+int pl_dyn_jac_device(pl_dyn* d, int fn, int batch, int frame, int flags, unsigned wrt, const void* in0,
+                      const void* in1, const void* in2, const void* in3, void* out, void* jac);
+
 /* ADMM linear-solve kernel.  All of them run the same OSQP 0.6 iteration on the same
  * block factor and agree to round-off; they differ in how the block-tridiagonal solve is
  * mapped to the GPU.  PL_ADMM_AUTO picks by batch size;

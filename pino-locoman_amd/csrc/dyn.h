@@ -63,25 +63,25 @@ PL_HD void dyn_in_len(const PlModel& M, int fn, int nf, int* len) {
 }
 
 // World placements (and local velocities when v != nullptr) of every joint frame.
-struct FkAll {
-  double oR[PL_MAXJ][9];
-  double op[PL_MAXJ][3];
-  double vl[PL_MAXJ][6];
+template <class S> struct FkAll {
+  S oR[PL_MAXJ][9];
+  S op[PL_MAXJ][3];
+  S vl[PL_MAXJ][6];
 };
-PL_HD void fk_all(const PlModel& M, const double* q, const double* v, FkAll& K) {
+template <class S> PL_HD void fk_all(const PlModel& M, const S* q, const S* v, FkAll<S>& K) {
   for (int j = 1; j < M.njoints; ++j) {
     const int par = M.parent[j];
-    double lR[9], lp[3], vJ[6];
+    S lR[9], lp[3], vJ[6];
     if (M.jtype[j] == PL_JT_FREEFLYER) {
       quat_to_R(q + M.idx_q[j] + 3, lR);
       for (int k = 0; k < 3; ++k) lp[k] = q[M.idx_q[j] + k];
-      for (int k = 0; k < 6; ++k) vJ[k] = v ? v[M.idx_v[j] + k] : 0.0;
+      for (int k = 0; k < 6; ++k) vJ[k] = v ? v[M.idx_v[j] + k] : S(0.0);
     } else {
-      double s, c;
+      S s, c;
       sincos_s(q[M.idx_q[j]], &s, &c);
       rev_rot(M, j, s, c, lR);
       for (int k = 0; k < 3; ++k) lp[k] = M.jp[j][k];
-      const double qd = v ? v[M.idx_v[j]] : 0.0;
+      const S qd = v ? v[M.idx_v[j]] : S(0.0);
       for (int k = 0; k < 3; ++k) { vJ[k] = 0.0; vJ[3 + k] = M.axis[j][k] * qd; }
     }
     if (par == 0) {
@@ -90,7 +90,7 @@ PL_HD void fk_all(const PlModel& M, const double* q, const double* v, FkAll& K) 
       for (int k = 0; k < 6; ++k) K.vl[j][k] = vJ[k];
     } else {
       matmul3(K.oR[par], lR, K.oR[j]);
-      double t[3];
+      S t[3];
       matvec(K.oR[par], lp, t);
       for (int k = 0; k < 3; ++k) K.op[j][k] = K.op[par][k] + t[k];
       act_inv_motion(lR, lp, K.vl[par], K.vl[j]);
@@ -99,46 +99,60 @@ PL_HD void fk_all(const PlModel& M, const double* q, const double* v, FkAll& K) 
   }
 }
 
-// oMf (rotation, translation) of frame F.
-PL_HD void frame_placement(const FkAll& K, const PlFrameRef& F, double* R, double* p) {
-  matmul3(K.oR[F.joint], F.R, R);
-  double t[3];
-  matvec(K.oR[F.joint], F.p, t);
-  for (int k = 0; k < 3; ++k) p[k] = K.op[F.joint][k] + t[k];
+// oMf (rotation, translation) of frame F on a joint at world placement (oR, op).
+template <class S> PL_HD void frame_placement(const S* oR, const S* op, const PlFrameRef& F, S* R, S* p) {
+  matmul3(oR, F.R, R);
+  S t[3];
+  matvec(oR, F.p, t);
+  for (int k = 0; k < 3; ++k) p[k] = op[k] + t[k];
+}
+template <class S> PL_HD void frame_placement(const FkAll<S>& K, const PlFrameRef& F, S* R, S* p) {
+  frame_placement(K.oR[F.joint], K.op[F.joint], F, R, p);
 }
 
-// getFrameVelocity(LOCAL_WORLD_ALIGNED): [R_j (v + w x p_f); R_j w]
-PL_HD void frame_vel_lwa(const FkAll& K, const PlFrameRef& F, double* out) {
-  const double* vj = K.vl[F.joint];
-  double wxp[3];
-  cross3(vj + 3, F.p, wxp);
-  double lv[3] = {vj[0] + wxp[0], vj[1] + wxp[1], vj[2] + wxp[2]};
-  matvec(K.oR[F.joint], lv, out);
-  matvec(K.oR[F.joint], vj + 3, out + 3);
+// getFrameVelocity(LOCAL_WORLD_ALIGNED): [R_j (v + w x p_f); R_j w], vj = the joint's local velocity
+template <class S> PL_HD void frame_vel_lwa(const S* oR, const S* vj, const PlFrameRef& F, S* out) {
+  S wxp[3];
+  const S fp[3] = {S(F.p[0]), S(F.p[1]), S(F.p[2])};
+  cross3(vj + 3, fp, wxp);
+  S lv[3] = {vj[0] + wxp[0], vj[1] + wxp[1], vj[2] + wxp[2]};
+  matvec(oR, lv, out);
+  matvec(oR, vj + 3, out + 3);
+}
+template <class S> PL_HD void frame_vel_lwa(const FkAll<S>& K, const PlFrameRef& F, S* out) {
+  frame_vel_lwa(K.oR[F.joint], K.vl[F.joint], F, out);
 }
 
-// Dynamics.get_frame_velocity(frame, relative_to_base) (dynamics/dynamics.py:77-118).
-PL_HD void frame_velocity(const FkAll& K, const PlFrameRef& F, const PlFrameRef& base, bool rel, double* out) {
-  double fv[6];
-  frame_vel_lwa(K, F, fv);
+// Dynamics.get_frame_velocity(frame, relative_to_base) (dynamics/dynamics.py:77-118), from the
+// states (oR, op, vl) of the frame's joint (f) and of the base frame's joint (b; read only if rel).
+template <class S>
+PL_HD void frame_velocity(const S* oRf, const S* opf, const S* vlf, const PlFrameRef& F, const S* oRb, const S* opb,
+                          const S* vlb, const PlFrameRef& base, bool rel, S* out) {
+  S fv[6];
+  frame_vel_lwa(oRf, vlf, F, fv);
   if (!rel) {
     for (int k = 0; k < 6; ++k) out[k] = fv[k];
     return;
   }
-  double bv[6], Rb[9], pb[3], Rf[9], pf[3];
-  frame_vel_lwa(K, base, bv);
-  frame_placement(K, base, Rb, pb);
-  frame_placement(K, F, Rf, pf);
-  double rel_p[3] = {pf[0] - pb[0], pf[1] - pb[1], pf[2] - pb[2]};
-  double corr[3];
+  S bv[6], Rb[9], pb[3], Rf[9], pf[3];
+  frame_vel_lwa(oRb, vlb, base, bv);
+  frame_placement(oRb, opb, base, Rb, pb);
+  frame_placement(oRf, opf, F, Rf, pf);
+  S rel_p[3] = {pf[0] - pb[0], pf[1] - pb[1], pf[2] - pb[2]};
+  S corr[3];
   cross3(bv + 3, rel_p, corr);
-  double rl[3], ra[3];
+  S rl[3], ra[3];
   for (int k = 0; k < 3; ++k) { rl[k] = fv[k] - bv[k] - corr[k]; ra[k] = fv[3 + k] - bv[3 + k]; }
-  double rlb[3], rab[3];
+  S rlb[3], rab[3];
   mattvec(Rb, rl, rlb);
   mattvec(Rb, ra, rab);
   out[0] = rlb[0]; out[1] = rlb[1]; out[2] = fv[2];
   out[3] = rab[0]; out[4] = rab[1]; out[5] = fv[5];
+}
+template <class S>
+PL_HD void frame_velocity(const FkAll<S>& K, const PlFrameRef& F, const PlFrameRef& base, bool rel, S* out) {
+  const int jb = rel ? base.joint : F.joint;
+  frame_velocity(K.oR[F.joint], K.op[F.joint], K.vl[F.joint], F, K.oR[jb], K.op[jb], K.vl[jb], base, rel, out);
 }
 
 // Full-array accessors for the tree passes.
@@ -161,24 +175,25 @@ PL_HD void rnea_full(const PlModel& M, const PlOcpConst& O, const double* q, con
 }
 
 // Solve the 6x6 system A x = b in place (Gaussian elimination, partial pivoting).
-PL_HD void solve6(double* A, double* b) {
+// The pivots follow the values (val()), as every data-dependent branch of the dual code does.
+template <class S> PL_HD void solve6(S* A, S* b) {
   for (int c = 0; c < 6; ++c) {
     int piv = c;
     for (int r = c + 1; r < 6; ++r)
-      if (fabs(A[6 * r + c]) > fabs(A[6 * piv + c])) piv = r;
+      if (fabs(val(A[6 * r + c])) > fabs(val(A[6 * piv + c]))) piv = r;
     if (piv != c) {
-      for (int k = 0; k < 6; ++k) { double t = A[6 * c + k]; A[6 * c + k] = A[6 * piv + k]; A[6 * piv + k] = t; }
-      double t = b[c]; b[c] = b[piv]; b[piv] = t;
+      for (int k = 0; k < 6; ++k) { S t = A[6 * c + k]; A[6 * c + k] = A[6 * piv + k]; A[6 * piv + k] = t; }
+      S t = b[c]; b[c] = b[piv]; b[piv] = t;
     }
-    const double inv = 1.0 / A[6 * c + c];
+    const S inv = 1.0 / A[6 * c + c];
     for (int r = c + 1; r < 6; ++r) {
-      const double fr = A[6 * r + c] * inv;
+      const S fr = A[6 * r + c] * inv;
       for (int k = c; k < 6; ++k) A[6 * r + k] -= fr * A[6 * c + k];
       b[r] -= fr * b[c];
     }
   }
   for (int r = 5; r >= 0; --r) {
-    double t = b[r];
+    S t = b[r];
     for (int k = r + 1; k < 6; ++k) t -= A[6 * r + k] * b[k];
     b[r] = t / A[6 * r + r];
   }
@@ -194,43 +209,43 @@ PL_HD void centroidal_full(const PlModel& M, const PlOcpConst& O, const double* 
 // d/dt h_G = A_G(q) a + dA_G/dt(q, v) v (pinocchio dccrba applied to v, plus A a):
 // Newton-Euler body forces without gravity, summed in world axes at the origin and
 // moved to the CoM (the CoM drift term vanishes: c_dot x m c_dot = 0).
-PL_HD void momentum_rate(const PlModel& M, const double* q, const double* v, const double* a, double* out) {
-  FkAll K;
+template <class S> PL_HD void momentum_rate(const PlModel& M, const S* q, const S* v, const S* a, S* out) {
+  FkAll<S> K;
   fk_all(M, q, v, K);
-  double acc[PL_MAXJ][6];
-  double Hd[6] = {0, 0, 0, 0, 0, 0}, mc[3] = {0, 0, 0};
+  S acc[PL_MAXJ][6];
+  S Hd[6] = {S(0.0), S(0.0), S(0.0), S(0.0), S(0.0), S(0.0)}, mc[3] = {S(0.0), S(0.0), S(0.0)};
   for (int j = 1; j < M.njoints; ++j) {
     const int par = M.parent[j];
-    double aj[6];
+    S aj[6];
     if (M.jtype[j] == PL_JT_FREEFLYER) {
       for (int k = 0; k < 6; ++k) aj[k] = a[M.idx_v[j] + k];  // c_J = 0, v x v_J = 0 for the root
     } else {
-      double s, c, lR[9];
+      S s, c, lR[9];
       sincos_s(q[M.idx_q[j]], &s, &c);
       rev_rot(M, j, s, c, lR);
       act_inv_motion(lR, M.jp[j], acc[par], aj);
-      const double qd = v[M.idx_v[j]], qdd = a[M.idx_v[j]];
+      const S qd = v[M.idx_v[j]], qdd = a[M.idx_v[j]];
       const double* ax = M.axis[j];
-      const double wJ[3] = {ax[0] * qd, ax[1] * qd, ax[2] * qd};
-      double t1[3], t2[3];
+      const S wJ[3] = {ax[0] * qd, ax[1] * qd, ax[2] * qd};
+      S t1[3], t2[3];
       cross3(K.vl[j], wJ, t1);      // v_lin x w_J
       cross3(K.vl[j] + 3, wJ, t2);  // w x w_J
       for (int k = 0; k < 3; ++k) { aj[k] += t1[k]; aj[3 + k] += ax[k] * qdd + t2[k]; }
     }
     for (int k = 0; k < 6; ++k) acc[j][k] = aj[k];
-    double fj[6], h[6], vxh[6];
+    S fj[6], h[6], vxh[6];
     inertia_mul(M.mass[j], M.lever[j], M.Ic[j], aj, fj);
     inertia_mul(M.mass[j], M.lever[j], M.Ic[j], K.vl[j], h);
     motion_cross_force(K.vl[j], h, vxh);
     for (int k = 0; k < 6; ++k) fj[k] += vxh[k];
-    double fw[6];
+    S fw[6];
     act_force(K.oR[j], K.op[j], fj, fw);
     for (int k = 0; k < 6; ++k) Hd[k] += fw[k];
-    double lc[3];
+    S lc[3];
     matvec(K.oR[j], M.lever[j], lc);
     for (int k = 0; k < 3; ++k) mc[k] += M.mass[j] * (K.op[j][k] + lc[k]);
   }
-  double com[3] = {mc[0] / M.total_mass, mc[1] / M.total_mass, mc[2] / M.total_mass}, cx[3];
+  S com[3] = {mc[0] / M.total_mass, mc[1] / M.total_mass, mc[2] / M.total_mass}, cx[3];
   cross3(com, Hd, cx);
   for (int k = 0; k < 3; ++k) { out[k] = Hd[k]; out[3 + k] = Hd[3 + k] - cx[k]; }
 }
@@ -259,9 +274,9 @@ PL_HD void aba_primal_column(const PlModel& M, const PlOcpConst& O, const double
   else rnea_full(M, O, q, v, z, u + nj, out);  // nle - J^T f
 }
 
-PL_HD void aba_primal_finish(const PlOcpConst& O, const double* dx, const double* raw, double* sh) {
-  const int nv = O.nv;
-  const double* u = dx + O.ndx;
+// raw -> sh (PL_ABA_SH): the factor of M and a = M^-1 ([0; tau_j] - raw's last column).
+PL_HD void aba_factor_solve(int nv, const double* tau_j, const double* raw, double* sh) {
+  const double* u = tau_j;
   const double* t0 = raw + nv * nv;
   const double* bq = raw + (nv + 1) * nv;
   double* L = sh + PL_MAXV;
@@ -282,6 +297,10 @@ PL_HD void aba_primal_finish(const PlOcpConst& O, const double* dx, const double
   }
   for (int k = 0; k < nv; ++k) sh[k] = (k < 6 ? 0.0 : u[k - 6]) - bq[k];
   chol_solve(L, nv, sh);
+}
+
+PL_HD void aba_primal_finish(const PlOcpConst& O, const double* dx, const double* raw, double* sh) {
+  aba_factor_solve(O.nv, dx + O.ndx, raw, sh);
 }
 
 // Serial form (host callers: the CPU baseline and the host row tests).
@@ -306,13 +325,13 @@ PL_HD void dyn_eval(const PlModel& M, const PlOcpConst& O, const PlFrameRef& F, 
       aba_forward<double>(M, O, in0, in1, ArrIn{in2}, ArrIn{in3}, out);
     } break;
     case PL_FN_FRAME_POS: {
-      FkAll K;
-      fk_all(M, in0, nullptr, K);
+      FkAll<double> K;
+      fk_all<double>(M, in0, nullptr, K);
       double R[9];
       frame_placement(K, F, R, out);
     } break;
     case PL_FN_FRAME_VEL: {
-      FkAll K;
+      FkAll<double> K;
       fk_all(M, in0, in1, K);
       frame_velocity(K, F, O.base, (flags & 2) != 0, out);
     } break;
@@ -396,7 +415,7 @@ PL_HD void dyn_eval(const PlModel& M, const PlOcpConst& O, const PlFrameRef& F, 
     case PL_FN_FRAME_JAC: {
       for (int c = 0; c < nv; ++c) {
         for (int k = 0; k < nv; ++k) e[k] = (k == c) ? 1.0 : 0.0;
-        FkAll K;
+        FkAll<double> K;
         fk_all(M, in0, e, K);
         double col[6];
         frame_vel_lwa(K, F, col);
@@ -413,8 +432,8 @@ PL_HD void dyn_eval(const PlModel& M, const PlOcpConst& O, const PlFrameRef& F, 
       }
     } break;
     case PL_FN_COM: {
-      FkAll K;
-      fk_all(M, in0, nullptr, K);
+      FkAll<double> K;
+      fk_all<double>(M, in0, nullptr, K);
       double mc[3] = {0, 0, 0};
       for (int j = 1; j < M.njoints; ++j) {
         double lc[3];

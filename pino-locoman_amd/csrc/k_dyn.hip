@@ -14,21 +14,10 @@
 
 #include "../../include/pinoloco.h"
 #include "dyn.h"
+#include "dyn_handle.h"
 #include "handles.h"
 #include "rows.h"
 #include "state.h"
-
-struct pl_dyn {
-  const pl_model* model;
-  PlModel M;
-  PlOcpConst O[2];   // contact frames: [0] feet only, [1] feet + external-force frame
-  int device;
-  hipStream_t stream;
-  PlModel* dM;
-  PlOcpConst* dO;
-  double* buf;
-  size_t cap;        // doubles in buf
-};
 
 __global__ __launch_bounds__(64) void k_dyn(const PlModel* M, const PlOcpConst* O, PlFrameRef F, int fn, int flags,
                                             int B, const double* in0, const double* in1, const double* in2,
@@ -109,28 +98,57 @@ extern "C" int pl_dyn_sizes(const pl_dyn* d, int fn, int flags, int* in_len, int
   return 0;
 }
 
-extern "C" int pl_dyn_eval(pl_dyn* d, int fn, int batch, int frame, int flags, const double* in0, const double* in1,
-                           const double* in2, const double* in3, double* out) {
-  if (!d || !out || batch < 0) { pl_set_error("bad arguments"); return -1; }
+// The checks pl_dyn_eval and pl_dyn_jac share: function code, flags, inputs present, frame.
+int pl_dyn_prepare(const pl_dyn* d, int fn, int frame, int flags, const void* const* in, int* len, PlFrameRef* F) {
   if (fn < 0 || fn >= PL_FN_COUNT) { pl_set_error("unknown dynamics function %d", fn); return -1; }
   if ((flags & 1) && !d->O[1].ext.valid) { pl_set_error("no external-force frame on this handle"); return -1; }
-  int len[4], lo = pl::dyn_out_len(d->M, fn);
   const PlOcpConst& O = d->O[flags & 1];
   pl::dyn_in_len(d->M, fn, O.nf, len);
-  const double* in[4] = {in0, in1, in2, in3};
   for (int k = 0; k < 4; ++k)
     if (len[k] > 0 && !in[k]) { pl_set_error("input %d missing", k); return -1; }
-  PlFrameRef F;
-  memset(&F, 0, sizeof(F));
+  memset(F, 0, sizeof(*F));
   const bool frame_fn = fn == PL_FN_FRAME_POS || fn == PL_FN_FRAME_VEL || fn == PL_FN_FRAME_JAC;
   if (frame_fn) {
-    F = frame_ref(d->model, frame);
-    if (!F.valid) { pl_set_error("invalid frame id %d", frame); return -1; }
+    *F = frame_ref(d->model, frame);
+    if (!F->valid) { pl_set_error("invalid frame id %d", frame); return -1; }
     if (fn == PL_FN_FRAME_VEL && (flags & 2) && !O.base.valid) {
       pl_set_error("relative_to_base needs the base_link frame");
       return -1;
     }
   }
+  return 0;
+}
+
+// Grow the handle's staging buffer to `need` doubles.
+int pl_dyn_reserve(pl_dyn* d, size_t need) {
+  if (need <= d->cap) return 0;
+  if (d->buf) hipFree(d->buf);
+  d->buf = nullptr;
+  d->cap = 0;
+  if (need > SIZE_MAX / sizeof(double)) { pl_set_error("staging buffer of %zu doubles overflows", need); return -2; }
+  PL_CHECK_HIP(hipMalloc(&d->buf, need * sizeof(double)));
+  d->cap = need;
+  return 0;
+}
+
+// k_dyn on the handle's stream, device pointers.
+int pl_dyn_launch_eval(pl_dyn* d, const PlFrameRef& F, int fn, int flags, int batch, const double* const* dptr,
+                       const int* len, double* dout, int lo) {
+  hipLaunchKernelGGL(k_dyn, dim3((batch + 63) / 64), dim3(64), 0, d->stream, d->dM, d->dO + (flags & 1), F, fn, flags,
+                     batch, dptr[0], dptr[1], dptr[2], dptr[3], len[0], len[1], len[2], len[3], dout, lo);
+  PL_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pl_dyn_eval(pl_dyn* d, int fn, int batch, int frame, int flags, const double* in0, const double* in1,
+                           const double* in2, const double* in3, double* out) {
+  if (!d || !out || batch < 0) { pl_set_error("bad arguments"); return -1; }
+  int len[4];
+  const double* in[4] = {in0, in1, in2, in3};
+  PlFrameRef F;
+  if (int rc = pl_dyn_prepare(d, fn, frame, flags, reinterpret_cast<const void* const*>(in), len, &F)) return rc;
+  const int lo = pl::dyn_out_len(d->M, fn);
+  const PlOcpConst& O = d->O[flags & 1];
   if (batch == 0) return 0;
   if (d->device < 0) {  // host handle
     for (int b = 0; b < batch; ++b)
@@ -143,13 +161,7 @@ extern "C" int pl_dyn_eval(pl_dyn* d, int fn, int batch, int frame, int flags, c
   (void)hipGetLastError();
   const size_t B = batch;
   const size_t need = B * ((size_t)len[0] + len[1] + len[2] + len[3] + lo);
-  if (need > d->cap) {
-    if (d->buf) hipFree(d->buf);
-    d->buf = nullptr;
-    d->cap = 0;
-    PL_CHECK_HIP(hipMalloc(&d->buf, need * sizeof(double)));
-    d->cap = need;
-  }
+  if (int rc = pl_dyn_reserve(d, need)) return rc;
   double* dptr[4];
   size_t off = 0;
   for (int k = 0; k < 4; ++k) {
@@ -158,9 +170,7 @@ extern "C" int pl_dyn_eval(pl_dyn* d, int fn, int batch, int frame, int flags, c
     off += B * len[k];
   }
   double* dout = d->buf + off;
-  hipLaunchKernelGGL(k_dyn, dim3((batch + 63) / 64), dim3(64), 0, d->stream, d->dM, d->dO + (flags & 1), F, fn, flags,
-                     batch, dptr[0], dptr[1], dptr[2], dptr[3], len[0], len[1], len[2], len[3], dout, lo);
-  PL_CHECK_HIP(hipGetLastError());
+  if (int rc = pl_dyn_launch_eval(d, F, fn, flags, batch, dptr, len, dout, lo)) return rc;
   PL_CHECK_HIP(hipMemcpyAsync(out, dout, B * lo * 8, hipMemcpyDeviceToHost, d->stream));
   PL_CHECK_HIP(hipStreamSynchronize(d->stream));
   return 0;

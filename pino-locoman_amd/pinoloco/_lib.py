@@ -158,6 +158,10 @@ EXPORTS = {
     "pl_dyn_destroy": (None, [C.c_void_p]),
     "pl_dyn_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip]),
     "pl_dyn_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pl_dyn_jac_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip]),
+    "pl_dyn_jac": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pl_dyn_jac_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -55,21 +55,79 @@ class PointFunction:
         self.out_shape = out_shape
 
     def __call__(self, *args):
-        if len(args) != len(self.in_len):
-            raise ValueError(f"{self.name} takes {len(self.in_len)} inputs ({self.in_len})")
-        arrs = [np.asarray(a, dtype=np.float64) for a in args]
-        single = all(a.ndim <= 1 for a in arrs)
-        B = 1 if single else max(a.shape[0] for a in arrs if a.ndim == 2)
-        ins = []
-        for a, n in zip(arrs, self.in_len):
-            a = np.ascontiguousarray(np.broadcast_to(a.reshape(-1, n) if a.ndim <= 1 else a, (B, n)))
-            ins.append(a)
+        ins, B, single = self._batch(args)
         out = np.zeros((B, self.out_len))
         ptrs = [_lib.dptr(a) for a in ins] + [None] * (4 - len(ins))
         _lib.check(_lib.lib().pl_dyn_eval(self._h.h, self._fn, B, self._frame, self._flags, *ptrs, _lib.dptr(out)))
         if self.out_shape:
             out = out.reshape((B,) + self.out_shape)
         return out[0] if single else out
+
+    def _batch(self, args):
+        if len(args) != len(self.in_len):
+            raise ValueError(f"{self.name} takes {len(self.in_len)} inputs ({self.in_len})")
+        arrs = [np.asarray(a, dtype=np.float64) for a in args]
+        single = all(a.ndim <= 1 for a in arrs)
+        B = 1 if single else max(a.shape[0] for a in arrs if a.ndim == 2)
+        ins = [np.ascontiguousarray(np.broadcast_to(a.reshape(-1, n) if a.ndim <= 1 else a, (B, n)))
+               for a, n in zip(arrs, self.in_len)]
+        return ins, B, single
+
+    def _wrt_mask(self, wrt):
+        sel = list(range(len(self.in_len))) if wrt is None else sorted({int(k) for k in wrt})
+        mask = 0
+        for k in sel:
+            if k < 0:
+                raise ValueError(f"{self.name}: wrt position {k}")
+            mask |= 1 << k
+        return sel, mask
+
+    def jacobian_sizes(self):
+        """(tan_len per input, out_len): a configuration input has tan_len = nv (pl_dyn_jac_sizes)."""
+        ins, tan, out = (C.c_int * 4)(), (C.c_int * 4)(), C.c_int()
+        _lib.check(_lib.lib().pl_dyn_jac_sizes(self._h.h, self._fn, self._flags, ins, tan, C.byref(out)))
+        return [int(t) for t, n in zip(tan, ins) if n > 0], int(out.value)
+
+    def jacobian(self, wrt=None, with_value=False):
+        """The Jacobian as a callable with this function's own argument list (the role of
+        ``ca.jacobian`` of the reference's point function, optimization/ocp.py:283-284).
+
+        ``wrt``: None for all inputs, or a sequence of input positions.  The callable returns a
+        tuple with one block per selected input, shaped ``[B, out_len, tan_len_k]``
+        (``[out_len, tan_len_k]`` for a single point); with ``with_value=True`` the value comes
+        first.  A configuration input is differentiated in its tangent space (``tan_len = nv``):
+        column k is d/d eps f(integrate(q, eps e_k)) at eps = 0, pinocchio's convention."""
+        sel, mask = self._wrt_mask(wrt)
+
+        def call(*args):
+            ins, B, single = self._batch(args)
+            tan, out_len = self.jacobian_sizes()
+            W = sum(tan[k] for k in sel if k < len(tan))
+            val = np.zeros((B, out_len)) if with_value else None
+            jac = np.zeros((B, out_len, max(W, 1)))
+            ptrs = [_lib.dptr(a) for a in ins] + [None] * (4 - len(ins))
+            _lib.check(_lib.lib().pl_dyn_jac(self._h.h, self._fn, B, self._frame, self._flags, mask, *ptrs,
+                                             _lib.dptr(val) if with_value else None, _lib.dptr(jac)))
+            blocks, off = [], 0
+            for k in sel:
+                blk = np.ascontiguousarray(jac[:, :, off:off + tan[k]])
+                blocks.append(blk[0] if single else blk)
+                off += tan[k]
+            if with_value:
+                blocks.insert(0, val[0] if single else val)
+            return tuple(blocks)
+
+        return call
+
+    def jacobian_device(self, batch, ins, jac, out=0, wrt=None):
+        """The same on caller-owned device memory: ``ins`` the inputs' device addresses (integers,
+        e.g. a torch tensor's data_ptr(), each ``[batch, in_len_k]`` float64), ``jac`` the address
+        of ``[batch, out_len, W]`` doubles, ``out`` optionally that of ``[batch, out_len]``.
+        Returns after the kernel has finished (pl_dyn_jac_device)."""
+        _, mask = self._wrt_mask(wrt)
+        ptrs = [C.c_void_p(int(p)) for p in ins] + [None] * (4 - len(ins))
+        _lib.check(_lib.lib().pl_dyn_jac_device(self._h.h, self._fn, int(batch), self._frame, self._flags, mask, *ptrs,
+                                                C.c_void_p(int(out)) if out else None, C.c_void_p(int(jac))))
 
 
 class Dynamics:
