@@ -548,6 +548,31 @@ int pl_ocp_set_admm_operands(pl_ocp* o, int mode);
 int pl_ocp_get_admm_operands(const pl_ocp* o);
 int pl_ocp_get_admm_rho_from_bounds(const pl_ocp* o);
 
+/* OSQP's adaptive_rho (OSQP 0.6.x compute_rho_estimate / adapt_rho / osqp_update_rho; the
+ * reference switches it off, optimization/ocp.py:267-273, and so does the default here).  Every
+ * problem of the batch holds its own rho, initialised to the handle's rho by pl_ocp_init_solver
+ * and by every call of the setter, and carried from one solve to the next (SQP iterations, MPC
+ * steps, warm-started solves) as OSQP carries settings->rho.  At every termination check whose
+ * iteration is a multiple of `interval`, a problem that the exact pass did not terminate
+ * estimates, on the solver's scaled quantities (infinity norms),
+ *   rho_est = clip(rho sqrt((|Ax - z| / (max(|z|, |Ax|) + 1e-10)) /
+ *                           (|Px + q + A'y| / (max(|q|, |A'y|, |Px|) + 1e-10) + 1e-10)), 1e-6, 1e6)
+ * and, iff rho_est > rho * tolerance or rho_est < rho / tolerance, takes it: the problem's row
+ * weights are rewritten by OSQP's classes, the problem is refactored and its right-hand side is
+ * rebuilt; the iterates are not touched.  At iteration max_iter the new rho serves the next solve.
+ * interval: 0 = check_termination, else a positive multiple of it (OSQP's automatic interval is a
+ * fraction of the measured setup time, not deterministic, and is not offered); tolerance > 1
+ * (OSQP: 5).  The setter fails with a message otherwise.  While the option is on, the fused sweep
+ * streams rho (pl_ocp_get_admm_rho_from_bounds is 0).  With PL_SOLVER_IP the settings are stored
+ * and have no effect.  pl_ocp_get_rho: per problem, rho, the last estimate and the number of
+ * updates in the last solve (any of the three may be null).
+ * pl_osqp_rho_estimate_host: the rule itself on the host, the code the kernel runs; norms =
+ * |Ax - z|, |z|, |Ax|, |Px + q + A'y|, |q|, |A'y|, |Px|. */
+int pl_ocp_set_adaptive_rho(pl_ocp* o, int enable, int interval, double tolerance);
+int pl_ocp_get_adaptive_rho(const pl_ocp* o, int* enable, int* interval, double* tolerance);
+int pl_ocp_get_rho(pl_ocp* o, double* rho, double* rho_estimate, int* updates);
+int pl_osqp_rho_estimate_host(const double norms[7], double rho, double tol, double* rho_est, int* update);
+
 /* Timing of the dominant kernel (ADMM sweeps) with HIP events on the handle's
  * stream: pl_ocp_profile(o, 1) clears and starts, pl_ocp_profile_read returns
  * [total_ms, launches, problem_iterations]. pl_ocp_sizes (out[13]): [n, m, nnz,

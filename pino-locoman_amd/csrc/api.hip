@@ -10,6 +10,7 @@
 #include "plant.h"
 #include "record.h"
 #include "retract.h"
+#include "rho_adapt.h"
 
 #include <map>
 
@@ -264,6 +265,7 @@ extern "C" int pl_ocp_create(const pl_model* model, const pl_ocp_desc* d, int ba
   h.admm_rc = 0;
   h.admm_operands = PL_ADMM_OPERANDS_FUSED;  // pl_ocp_set_admm_operands: _SPLIT is the earlier path
   h.admm_rho_rule = 0;                       // nothing has written d.rho yet
+  h.ra.tol = 5.0;                            // adaptive rho: off (pl_ocp_set_adaptive_rho), OSQP's tolerance
   h.rc_waves = 8;
   h.ruiz_fused = !(h.debug_paths & PL_PATH_RUIZ_PER_PASS);
   h.ch_stride = rc_ch_stride(h.N, h.ndx, h.rc_waves);
@@ -520,6 +522,7 @@ extern "C" int pl_ocp_init_solver(pl_ocp* o) {
   launch_hess(&o->h);
   launch_reset_iterates(&o->h);
   launch_reset_info(&o->h);
+  if (o->h.ra.rho_b) launch_rho_reset(&o->h, 1);  // every problem back to the handle's rho
   PL_CHECK_HIP(hipGetLastError());
   PL_CHECK_HIP(hipStreamSynchronize(o->h.stream));
   return 0;
@@ -539,6 +542,7 @@ static int enqueue_solve(pl_ocp* o, bool timed) {
   if (timed) hipEventRecord(o->ev[2], h->stream);
   // osqp.solve() (ocp.py:401)
   launch_reset_info(h);
+  if (rho_adapt_on(h)) launch_rho_reset(h, 0);  // the update counts are per solve; rho_b carries over
   if (!h->set.warm_start) launch_reset_iterates(h);
   launch_admm_init(h);
   const int ct = h->set.check_termination > 0 ? h->set.check_termination : h->set.max_iter;
@@ -550,6 +554,19 @@ static int enqueue_solve(pl_ocp* o, bool timed) {
     const bool at_check = (h->set.check_termination > 0 && it % h->set.check_termination == 0);
     launch_admm(h, nit, (at_check || final) ? 1 : 0, it - nit);
     if (at_check || final) launch_check(h, it, final ? 1 : 0);
+    if ((at_check || final) && rho_adapt_at(h, it)) {
+      // adaptive rho: the problems the exact pass left running re-estimate their rho; those that
+      // leave the band are refactored (the host does not know which: the launches are masked on
+      // the device and enqueued every time) and get their carried rhs rebuilt with the new rho
+      launch_rho_adapt(h, it, final ? 1 : 0);
+      if (!final) {
+        h->d.ipskip = h->ra.mask;
+        launch_factor_core(h);
+        h->d.ipskip = nullptr;
+        if (h->admm_rc) launch_fred_masked(h, h->ra.mask);
+        launch_admm_init_masked(h, h->ra.mask);
+      }
+    }
   }
   launch_unscale(h);
   if (timed) hipEventRecord(o->ev[3], h->stream);
@@ -622,7 +639,85 @@ extern "C" int pl_ocp_get_admm_operands(const pl_ocp* o) {
 // PL_ADMM_OPERANDS_SPLIT.
 extern "C" int pl_ocp_get_admm_rho_from_bounds(const pl_ocp* o) {
   if (!o) { pl_set_error("null handle"); return -1; }
-  return o->h.admm_operands == PL_ADMM_OPERANDS_FUSED && o->h.admm_rho_rule ? 1 : 0;
+  return o->h.admm_operands == PL_ADMM_OPERANDS_FUSED && o->h.admm_rho_rule && !rho_adapt_on(&o->h) ? 1 : 0;
+}
+
+// OSQP adaptive rho (rho_adapt.h, k_rho.hip).  The settings are stored on any handle; a device
+// handle allocates the per-problem state on the first enabling call, and every call puts every
+// problem's rho back to the handle's.  With PL_SOLVER_IP they have no effect (the interior point
+// writes its own row weights).
+extern "C" int pl_ocp_set_adaptive_rho(pl_ocp* o, int enable, int interval, double tolerance) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  PlOcpHandle* h = &o->h;
+  if (enable != 0 && enable != 1) { pl_set_error("adaptive_rho %d: must be 0 or 1", enable); return -1; }
+  const int ct = h->set.check_termination;
+  if (interval < 0 || (interval > 0 && (ct <= 0 || interval % ct != 0))) {
+    pl_set_error("adaptive_rho_interval %d: must be 0 (= check_termination) or a positive multiple of "
+                 "check_termination (%d)", interval, ct);
+    return -1;
+  }
+  if (!(tolerance > 1.0)) { pl_set_error("adaptive_rho_tolerance %g: must be > 1", tolerance); return -1; }
+  if (o->on_device) {
+    (void)hipSetDevice(h->device);
+    (void)hipGetLastError();
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+    if (enable && !h->ra.rho_b) {
+      const size_t B = h->B;
+      PlRhoAdapt ra = h->ra;
+      if (dalloc(o, &ra.rho_b, B) || dalloc(o, &ra.rho_est, B) || dalloc(o, &ra.nupd, B) ||
+          dalloc(o, &ra.upd_it, B * PL_RHO_LOG) || dalloc(o, &ra.sn, B * (size_t)(h->N + 1) * 8) ||
+          dalloc(o, &ra.mask, B))
+        return -2;
+      h->ra = ra;
+    }
+  }
+  h->ra.enable = enable;
+  h->ra.interval = interval;
+  h->ra.tol = tolerance;
+  if (o->on_device && h->ra.rho_b) {
+    launch_rho_reset(h, 1);
+    PL_CHECK_HIP(hipGetLastError());
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+extern "C" int pl_ocp_get_adaptive_rho(const pl_ocp* o, int* enable, int* interval, double* tolerance) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (enable) *enable = o->h.ra.enable;
+  if (interval) *interval = o->h.ra.interval;
+  if (tolerance) *tolerance = o->h.ra.tol;
+  return 0;
+}
+
+// Per problem: rho, the last estimate and the updates of the last solve.  Before the option was
+// ever enabled every problem holds the handle's rho and has made no update.
+extern "C" int pl_ocp_get_rho(pl_ocp* o, double* rho, double* rho_estimate, int* updates) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  const size_t B = h->B;
+  if (!h->ra.rho_b) {
+    for (size_t b = 0; b < B; ++b) {
+      if (rho) rho[b] = h->set.rho;
+      if (rho_estimate) rho_estimate[b] = h->set.rho;
+      if (updates) updates[b] = 0;
+    }
+    return 0;
+  }
+  if (rho) PL_CHECK_HIP(hipMemcpyAsync(rho, h->ra.rho_b, B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (rho_estimate) PL_CHECK_HIP(hipMemcpyAsync(rho_estimate, h->ra.rho_est, B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (updates) PL_CHECK_HIP(hipMemcpyAsync(updates, h->ra.nupd, B * 4, hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The device's rule on the host (tests): nrm = the seven scaled norms of rho_adapt.h.
+extern "C" int pl_osqp_rho_estimate_host(const double nrm[7], double rho, double tol, double* rho_est, int* update) {
+  if (!nrm || !rho_est || !update) { pl_set_error("null argument"); return -1; }
+  const double est = pl::rho_estimate(nrm, rho);
+  *rho_est = est;
+  *update = pl::rho_update(est, rho, tol) ? 1 : 0;
+  return 0;
 }
 
 extern "C" int pl_ocp_get_admm_groups(const pl_ocp* o) {
@@ -1882,6 +1977,7 @@ static int debug_rw(pl_ocp* o, const char* name, double* out, const double* in, 
       {"dxs", h->d.dxs, B * h->n}, {"dys", h->d.dys, B * h->m},     {"chk", h->d.chk, B * (size_t)(h->N + 1) * 8},
       {"lbg", h->d.lbg, B * h->m}, {"ubg", h->d.ubg, B * h->m},
       {"rhoc", h->d.rhoc, B * (size_t)(h->N + 1) * std::max(h->ncpl_max, 1)},
+      {"rho_upd_it", h->ra.upd_it, h->ra.upd_it ? B * PL_RHO_LOG : 0},
       {"ip_s", h->d.ip_s, h->d.ip_s ? B * h->m : 0},     {"ip_lam", h->d.ip_lam, h->d.ip_lam ? B * h->m : 0},
       {"ip_lam0", h->d.ip_lam0, h->d.ip_lam0 ? B * h->m : 0},
       {"ip_zl", h->d.ip_zl, h->d.ip_zl ? B * h->m : 0},  {"ip_zu", h->d.ip_zu, h->d.ip_zu ? B * h->m : 0},

@@ -166,9 +166,10 @@ __device__ __forceinline__ void lds_barrier() {
 // F_i[a][k] = sum_{(e, s) in xc(a)} A_e rho_s sum_{(e', l) in cw(s)} A_e' S_i[l][k]
 // (the coupling product the sweep kernels apply as t_s = rho_s a_s(w) . w).
 __global__ __launch_bounds__(256) void k_fred(PlDev d, int N, int nnz, int ndx, int S_stride, int cpl_stride,
-                                              long long ch_stride, RcMap mp) {
+                                              long long ch_stride, RcMap mp, const PlIpInfo* only) {
   extern __shared__ double sc[];  // S_i[:, 0:ndx] dense, sc[l * ndx + k]; then F_i
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
+  if (only && !only[b].active) return;  // masked refactor (adaptive rho): null = every problem
   typedef const __attribute__((address_space(4))) PlAdmmNode* CNode;
   const CNode an = (CNode)d.anodes;
   const int nw = an[i].nw, K = an[i].nunit;
@@ -985,7 +986,9 @@ bool admm_rc_supported(const PlOcpHandle* h) {
          rc_config(h, h->rc_waves).lm.asb_cap >= (2 * h->N + 3) * ((h->ndx + h->rc_waves - 1) / h->rc_waves);  // chain history
 }
 
-void launch_fred(PlOcpHandle* h) {
+void launch_fred(PlOcpHandle* h) { launch_fred_masked(h, nullptr); }
+
+void launch_fred_masked(PlOcpHandle* h, const PlIpInfo* mask) {
   const size_t lds = (size_t)(h->nw_max + h->ndx) * h->ndx * sizeof(double);
   static bool attr = false;
   if (!attr) {
@@ -993,7 +996,7 @@ void launch_fred(PlOcpHandle* h) {
     attr = true;
   }
   hipLaunchKernelGGL(k_fred, dim3(h->B * (h->N + 1)), dim3(256), lds, h->stream, h->d, h->N, h->nnz, h->ndx,
-                     h->S_stride, std::max(h->ncpl_max, 1), h->ch_stride, rc_map(h->ndx, h->rc_waves));
+                     h->S_stride, std::max(h->ncpl_max, 1), h->ch_stride, rc_map(h->ndx, h->rc_waves), mask);
 }
 
 void launch_admm_rc(PlOcpHandle* h, int niter, int check) {

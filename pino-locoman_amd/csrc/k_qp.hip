@@ -427,6 +427,7 @@ __global__ __launch_bounds__(256) void k_qp_finish(PlDev d, int N, int n, int m,
 void launch_qp_setup(PlOcpHandle* h) {
   const dim3 nodes_grid(h->B * (h->N + 1));
   h->admm_rho_rule = 1;  // k_qp_finish (below, on both paths) writes d.rho by its rule on ls, us
+  if (rho_adapt_on(h)) h->admm_rho_rule = 0;  // launch_rho_rows rewrites it with the per-problem rho: streamed
   if (h->ruiz_fused && ruiz_fused_supported(h)) {
     static bool fattr = false;
     if (!fattr) {
@@ -437,6 +438,7 @@ void launch_qp_setup(PlOcpHandle* h) {
                        h->set.scaling);
     hipLaunchKernelGGL(k_qp_finish, nodes_grid, dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
                        std::max(h->ncpl_max, 1), h->set);
+    if (rho_adapt_on(h)) launch_rho_rows(h);
     return;
   }
   hipLaunchKernelGGL(k_ruiz_init, dim3(h->B), dim3(256), 0, h->stream, h->d, h->n, h->m);
@@ -455,13 +457,18 @@ void launch_qp_setup(PlOcpHandle* h) {
   }
   hipLaunchKernelGGL(k_qp_finish, nodes_grid, dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
                      std::max(h->ncpl_max, 1), h->set);
+  if (rho_adapt_on(h)) launch_rho_rows(h);
 }
 
 // rhs = sigma x - q + A^T (rho z - y)   (before the first iteration of a solve)
 // zero (the interior point's refinement sweeps): z = y = 0, so A^T (rho z - y) adds nothing
 // and the gathers are skipped (rhs = sigma x - q, the same value up to the sign of a zero)
-__global__ __launch_bounds__(256) void k_admm_init(PlDev d, int N, int n, int m, int nnz, double sigma, int zero) {
+// only (the adaptive rho's rebuild after a masked refactor): null = every problem, else the
+// problems whose `active` is set
+__global__ __launch_bounds__(256) void k_admm_init(PlDev d, int N, int n, int m, int nnz, double sigma, int zero,
+                                                   const PlIpInfo* only) {
   const int b = blockIdx.x;
+  if (only && !only[b].active) return;
   if (d.info[b].done) return;
   const double* As = d.As + (size_t)b * nnz;
   const double* za = d.za + (size_t)b * m;
@@ -502,12 +509,16 @@ __global__ __launch_bounds__(256) void k_admm_init(PlDev d, int N, int n, int m,
 
 void launch_admm_init(PlOcpHandle* h) {
   hipLaunchKernelGGL(k_admm_init, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
-                     h->set.sigma, 0);
+                     h->set.sigma, 0, (const PlIpInfo*)nullptr);
+}
+void launch_admm_init_masked(PlOcpHandle* h, const PlIpInfo* mask) {
+  hipLaunchKernelGGL(k_admm_init, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
+                     h->set.sigma, 0, mask);
 }
 // (k_ip.hip) the refinement sweeps: x = z = y = 0
 void launch_admm_init_zero(PlOcpHandle* h) {
   hipLaunchKernelGGL(k_admm_init, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
-                     h->set.sigma, 1);
+                     h->set.sigma, 1, (const PlIpInfo*)nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -530,7 +541,10 @@ __device__ __forceinline__ void chk_lds_add(double* p, double v) {
   __hip_atomic_fetch_add((LPtr)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
-__global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m, int nnz, int ndx) {
+// SC (the adaptive rho's checks): also the maxima of the SCALED quantities, in the same order,
+// to sn[b][i][0..6] (rho_adapt.h); d.chk is written exactly as without it.
+template <bool SC>
+__global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m, int nnz, int ndx, double* sn) {
   extern __shared__ double lds[];
   const int b = blockIdx.x / (N + 1), i = blockIdx.x - b * (N + 1);
   if (d.info[b].done) return;
@@ -575,6 +589,7 @@ __global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m,
   }
   __syncthreads();
   double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double sv[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   {
     const double* za = d.za + (size_t)b * m + nd.row_off;
     const double* E = d.E + (size_t)b * m + nd.row_off;
@@ -583,6 +598,11 @@ __global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m,
       v[0] = fmax(v[0], fabs(ei * (axr - zr)));
       v[1] = fmax(v[1], fabs(ei * zr));
       v[2] = fmax(v[2], fabs(ei * axr));
+      if constexpr (SC) {
+        sv[0] = fmax(sv[0], fabs(axr - zr));
+        sv[1] = fmax(sv[1], fabs(zr));
+        sv[2] = fmax(sv[2], fabs(axr));
+      }
     }
   }
   {
@@ -597,6 +617,12 @@ __global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m,
       v[4] = fmax(v[4], fabs(di * qc));
       v[5] = fmax(v[5], fabs(di * atyc));
       v[6] = fmax(v[6], fabs(di * px));
+      if constexpr (SC) {
+        sv[3] = fmax(sv[3], fabs(px + qc + atyc));
+        sv[4] = fmax(sv[4], fabs(qc));
+        sv[5] = fmax(sv[5], fabs(atyc));
+        sv[6] = fmax(sv[6], fabs(px));
+      }
     }
   }
   // one wave: butterfly maxima across the 64 lanes (max is order-free, so exact)
@@ -608,6 +634,16 @@ __global__ __launch_bounds__(64) void k_check_part(PlDev d, int N, int n, int m,
 #pragma unroll
   for (int k = 0; k < 7; ++k)
     if (tid == k) out[k] = v[k];
+  if constexpr (SC) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+      for (int k = 0; k < 7; ++k) sv[k] = fmax(sv[k], __shfl_xor(sv[k], s, 64));
+    double* so = sn + ((size_t)b * (N + 1) + i) * 8;
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+      if (tid == k) so[k] = sv[k];
+  }
 }
 
 // Termination (OSQP 0.6 update_info + check_termination, incl. infeasibility
@@ -736,11 +772,14 @@ __global__ __launch_bounds__(CHECK_NT) void k_check(PlDev d, int N, int n, int m
 }
 
 void launch_check(PlOcpHandle* h, int it, int final_check) {
-  (void)it;
   {
     const int lds = ((std::max(h->ncol_max, h->nw_max) + 1) & ~1) + ((h->nrow_max + 1) & ~1) + ((h->nw_max + 1) & ~1);
-    hipLaunchKernelGGL(k_check_part, dim3(h->B * (h->N + 1)), dim3(64), lds * 8, h->stream, h->d, h->N, h->n, h->m,
-                       h->nnz, h->ndx);
+    if (rho_adapt_at(h, it))  // the scaled norms too, for k_rho_adapt
+      hipLaunchKernelGGL(k_check_part<true>, dim3(h->B * (h->N + 1)), dim3(64), lds * 8, h->stream, h->d, h->N, h->n,
+                         h->m, h->nnz, h->ndx, h->ra.sn);
+    else
+      hipLaunchKernelGGL(k_check_part<false>, dim3(h->B * (h->N + 1)), dim3(64), lds * 8, h->stream, h->d, h->N, h->n,
+                         h->m, h->nnz, h->ndx, (double*)nullptr);
   }
   hipLaunchKernelGGL(k_check, dim3(h->B), dim3(CHECK_NT), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz, h->set,
                      final_check);

@@ -86,6 +86,7 @@ struct PlNode {
 #define PL_OSQP_INFTY 1e30
 #define PL_MIN_SCALING 1e-4
 #define PL_RHO_MIN 1e-6
+#define PL_RHO_MAX 1e6
 #define PL_RHO_TOL 1e-4
 #define PL_RHO_EQ_OVER_INEQ 1e3
 struct PlAdmmNode {
@@ -283,8 +284,22 @@ struct PlDev {
 };
 
 // an interior-point solve's terminated problem (PlDev::ipskip): nothing downstream reads its
-// evaluation or factor any more
+// evaluation or factor any more.  The masked refactor of the adaptive rho points d.ipskip at
+// PlRhoAdapt::mask for its factor launches: `active` = the problem's rho changed.
 __device__ inline bool ip_skip(const PlDev& d, int b) { return d.ipskip && !d.ipskip[b].active; }
+
+// OSQP adaptive rho: settings and per-problem state.  interval 0 = check_termination.
+#define PL_RHO_LOG 8  // update iterations kept per problem and solve (pl_debug_get "rho_upd_it")
+struct PlRhoAdapt {
+  int enable, interval;
+  double tol;
+  double* rho_b;     // [B] the problem's rho: carried from solve to solve (OSQP's settings->rho)
+  double* rho_est;   // [B] the last estimate
+  int* nupd;         // [B] updates in the current solve
+  double* upd_it;    // [B][PL_RHO_LOG] iteration of each of them (0: none)
+  double* sn;        // [B][N + 1][8] scaled residual-norm partials (k_check_part<true>)
+  PlIpInfo* mask;    // [B] `active` = refactor this problem (the factor kernels' per-problem mask)
+};
 
 
 struct PlOcpHandle {
@@ -357,6 +372,10 @@ struct PlOcpHandle {
   int plant_substeps;               // Euler substeps of dt_min, [1, 16]
   int plant_noise_on;               // 1: k_mpc_prepare writes x_init = state_integrate(x_state, noise)
   int plant_contact_on;             // 1: PL_PLANT_ABA runs k_plant's contact instantiation (pl_mpc_set_contact)
+  // OSQP adaptive rho (pl_ocp_set_adaptive_rho, rho_adapt.h, k_rho.hip); inside the key too: a
+  // change of the settings changes the launch sequence.  The buffers are allocated by the first
+  // enabling call on a device handle and never move afterwards.
+  PlRhoAdapt ra;
   PlDev d;
   // host copies of the structure
   int* h_nodes_raw;
@@ -417,6 +436,18 @@ long long rc_ch_stride(int N, int ndx, int W);
 int rc_chv_stride(int N, int ndx);
 int rc_groups(const PlOcpHandle* h);
 void launch_check(PlOcpHandle* h, int it, int final_check);
+// OSQP adaptive rho (k_rho.hip).  On: the OSQP solver with the option set on a device handle.
+// A problem may adapt at the checks whose iteration is a multiple of the interval.
+inline bool rho_adapt_on(const PlOcpHandle* h) { return h->solver == 0 && h->ra.enable && h->ra.rho_b; }
+inline bool rho_adapt_at(const PlOcpHandle* h, int it) {
+  const int iv = h->ra.interval > 0 ? h->ra.interval : h->set.check_termination;
+  return rho_adapt_on(h) && iv > 0 && it > 0 && it % iv == 0;
+}
+void launch_rho_reset(PlOcpHandle* h, int full);  // full: rho_b = rho_est = settings rho; always: no updates yet
+void launch_rho_rows(PlOcpHandle* h);             // d.rho, d.rhoc by the row classes with rho_b (after k_qp_finish)
+void launch_rho_adapt(PlOcpHandle* h, int it, int final_check);
+void launch_fred_masked(PlOcpHandle* h, const PlIpInfo* mask);       // mask: null = every problem
+void launch_admm_init_masked(PlOcpHandle* h, const PlIpInfo* mask);
 void launch_unscale(PlOcpHandle* h);
 void launch_line_search(PlOcpHandle* h);
 void launch_mpc_prepare(PlOcpHandle* h, int k);

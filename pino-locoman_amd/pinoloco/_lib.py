@@ -101,7 +101,11 @@ EXPORTS = {
     "pl_ocp_set_admm_operands": (C.c_int, [C.c_void_p, C.c_int]),
     "pl_ocp_get_admm_operands": (C.c_int, [C.c_void_p]),
     "pl_ocp_get_admm_rho_from_bounds": (C.c_int, [C.c_void_p]),
-    "pl_ocp_set_ip_settings": (C.c_int, [C.c_void_p, C.POINTER(IpSettings)]),
+    "pl_ocp_set_adaptive_rho": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "pl_ocp_get_adaptive_rho": (C.c_int, [C.c_void_p, _ip, _ip, _dp]),
+    "pl_ocp_get_rho": (C.c_int, [C.c_void_p, _dp, _dp, _ip]),
+    "pl_osqp_rho_estimate_host": (C.c_int, [_dp, C.c_double, C.c_double, _dp, _ip]),
+    "pl_ocp_set_ip_settings":(C.c_int, [C.c_void_p, C.POINTER(IpSettings)]),
     "pl_ocp_ip_stats": (C.c_int, [C.c_void_p, C.POINTER(IpStats)]),
     "pl_ocp_get_lam": (C.c_int, [C.c_void_p, _dp]),
     "pl_ocp_set_lam": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 LIB = os.path.join(HERE, "libpinoloco.so")
 SOURCES = ["api.hip", "api_build.hip", "api_casadi.hip", "k_eval.hip", "k_qp.hip", "k_admm.hip", "k_factor.hip", "k_dyn.hip", "k_admm2.hip", "k_ip.hip", "k_admm_rc.hip", "k_hess.hip", "k_retract.hip", "k_plant.hip",
-           "k_record.hip", "k_dyn_jac.hip"]
+           "k_record.hip", "k_dyn_jac.hip", "k_rho.hip"]
 ARCH = os.environ.get("PL_OFFLOAD_ARCH", "gfx950")
 
 

@@ -235,6 +235,13 @@ class BatchedOCP:
         _lib.check(L.pl_ocp_dims(h, C.byref(n), C.byref(m), C.byref(np_), C.byref(nnz)))
         self.n, self.m, self.np, self.nnz = n.value, m.value, np_.value, nnz.value
         assert self.n == self.layout.n and self.np == self.layout.np, (self.n, self.layout.n, self.np, self.layout.np)
+        if s["adaptive_rho"] or "adaptive_rho_interval" in s or "adaptive_rho_tolerance" in s:
+            try:
+                self.set_adaptive_rho(bool(s["adaptive_rho"]), int(s.get("adaptive_rho_interval", 0)),
+                                      float(s.get("adaptive_rho_tolerance", 5.0)))
+            except Exception:
+                self.close()
+                raise
 
     # ---------------------------------------------------------------- queries
     def pattern(self):
@@ -317,6 +324,30 @@ class BatchedOCP:
         """True when a fused sweep launched now would compute rho from the bounds (the OSQP
         path wrote it), False when it would stream it (interior-point weights, "split")."""
         return bool(_lib.lib().pl_ocp_get_admm_rho_from_bounds(self.h))
+
+    def set_adaptive_rho(self, enable=True, interval=0, tolerance=5.0):
+        """OSQP's adaptive_rho (off by default, as the reference sets it, ocp.py:267-273): every
+        problem re-estimates its own rho from the residual ratio at the termination checks whose
+        iteration is a multiple of `interval` (0: check_termination; else a positive multiple of
+        it) and, when the estimate leaves [rho / tolerance, rho * tolerance], is refactored.  The
+        call puts every problem's rho back to the handle's.  No effect with the "fatrop" solver."""
+        _lib.check(_lib.lib().pl_ocp_set_adaptive_rho(self.h, int(bool(enable)), int(interval), float(tolerance)))
+        self.settings.update(adaptive_rho=bool(enable), adaptive_rho_interval=int(interval),
+                             adaptive_rho_tolerance=float(tolerance))
+
+    def adaptive_rho(self):
+        """(enable, interval, tolerance) as the handle holds them."""
+        e, i, t = C.c_int(), C.c_int(), C.c_double()
+        _lib.check(_lib.lib().pl_ocp_get_adaptive_rho(self.h, C.byref(e), C.byref(i), C.byref(t)))
+        return bool(e.value), i.value, t.value
+
+    def osqp_rho(self):
+        """Per problem: "rho" (carried to the next solve), "rho_estimate" (the last estimate) and
+        "updates" (rho updates in the last solve)."""
+        rho, est = np.zeros(self.batch), np.zeros(self.batch)
+        upd = np.zeros(self.batch, dtype=np.int32)
+        _lib.check(_lib.lib().pl_ocp_get_rho(self.h, _lib.dptr(rho), _lib.dptr(est), _lib.iptr(upd)))
+        return {"rho": rho, "rho_estimate": est, "updates": upd}
 
     def set_solver(self, solver):
         """"osqp" (SQP + OSQP, ocp.py:265-313 / 375-422) or "fatrop" (the interior-point
@@ -911,7 +942,8 @@ class CompiledSolver:
 class OCP:
     """Single-problem OCP with the reference's method surface (ocp.py:11-480)."""
 
-    def __init__(self, robot, solver, nodes, dynamics, tau_nodes=3, include_acc=True, include_base=True, device=0):
+    def __init__(self, robot, solver, nodes, dynamics, tau_nodes=3, include_acc=True, include_base=True, device=0,
+                 osqp_settings=None):
         if solver not in SOLVER_CODES:
             raise ValueError(f"Solver {solver} not supported (ocp.py:248, 265: 'fatrop' or 'osqp')")
         self.robot = robot
@@ -953,7 +985,8 @@ class OCP:
         self._backend = BatchedOCP(robot, dynamics, nodes, batch=1, device=device, tau_nodes=tau_nodes,
                                    include_acc=include_acc, include_base=include_base,
                                    gait_type=self.gait_sequence.gait_type if self.gait_sequence else "trot",
-                                   gait_period=self.gait_sequence.gait_period if self.gait_sequence else 0.8)
+                                   gait_period=self.gait_sequence.gait_period if self.gait_sequence else 0.8,
+                                   osqp_settings=osqp_settings)
         if solver == "fatrop" and device >= 0:  # a host-only handle (device < 0) never solves
             self._backend.set_solver("fatrop")
             self._backend.set_ip_settings()
@@ -1143,18 +1176,19 @@ class OCP:
 
 
 class OCPWholeBodyRNEA(OCP):
-    def __init__(self, robot, solver, nodes, tau_nodes, include_acc=True):
-        super().__init__(robot, solver, nodes, "whole_body_rnea", tau_nodes=tau_nodes, include_acc=include_acc)
+    def __init__(self, robot, solver, nodes, tau_nodes, include_acc=True, osqp_settings=None):
+        super().__init__(robot, solver, nodes, "whole_body_rnea", tau_nodes=tau_nodes, include_acc=include_acc,
+                         osqp_settings=osqp_settings)
 
 
 class OCPWholeBodyAcc(OCP):
-    def __init__(self, robot, solver, nodes, include_base=False):
-        super().__init__(robot, solver, nodes, "whole_body_acc", include_base=include_base)
+    def __init__(self, robot, solver, nodes, include_base=False, osqp_settings=None):
+        super().__init__(robot, solver, nodes, "whole_body_acc", include_base=include_base, osqp_settings=osqp_settings)
 
 
 class OCPWholeBodyABA(OCP):
-    def __init__(self, robot, solver, nodes):
-        super().__init__(robot, solver, nodes, "whole_body_aba")
+    def __init__(self, robot, solver, nodes, osqp_settings=None):
+        super().__init__(robot, solver, nodes, "whole_body_aba", osqp_settings=osqp_settings)
 
 
 class OCPCentroidalVel(OCP):
@@ -1162,8 +1196,8 @@ class OCPCentroidalVel(OCP):
     include_base=False (the class default), u = [v_j | forces] and the base velocity
     v_b = A_b^-1 (m h - A_j v_j) inside the rows (ocp_centroidal_vel.py:119-129)."""
 
-    def __init__(self, robot, solver, nodes, include_base=False):
-        super().__init__(robot, solver, nodes, "centroidal_vel", include_base=include_base)
+    def __init__(self, robot, solver, nodes, include_base=False, osqp_settings=None):
+        super().__init__(robot, solver, nodes, "centroidal_vel", include_base=include_base, osqp_settings=osqp_settings)
         self.nv_opt = self.layout.nv_opt
 
     def retract_stacked_sol(self, sol_x, retract_all=True):
@@ -1211,8 +1245,8 @@ class OCPCentroidalAcc(OCP):
     equations in centroidal form: the gap A a + dA v - dh (include_base) or the base
     acceleration A_b^-1 (dh - dA v - A_j a_j) (pinocchio computeCentroidalMap / dccrba)."""
 
-    def __init__(self, robot, solver, nodes, include_base=False):
-        super().__init__(robot, solver, nodes, "centroidal_acc", include_base=include_base)
+    def __init__(self, robot, solver, nodes, include_base=False, osqp_settings=None):
+        super().__init__(robot, solver, nodes, "centroidal_acc", include_base=include_base, osqp_settings=osqp_settings)
 
 
 def make_ocp(dynamics, default_args, **kwargs):
