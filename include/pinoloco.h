@@ -601,6 +601,30 @@ int pl_debug_qp_setup(pl_ocp* o);
 /* One termination check on the current iterates and scaled data, then (unscale) the step
  * write-back; read status / pri_res / dua_res with pl_mpc_get_stats. */
 int pl_debug_check(pl_ocp* o, int final_check, int unscale);
+/* Interior-point stage tests: exactly one stage of the interior-point iteration on the device
+ * buffers as they are (pl_ocp_set_solver(o, PL_SOLVER_IP) first), then a synchronise.
+ *   PL_IP_STAGE_INIT     k_ip_init with warm = arg, on the current "g", "lbg", "ubg" (and
+ *                        "ip_lam0"); nothing is evaluated first
+ *   PL_IP_STAGE_KKT      k_ip_kkt of iteration k = arg >= 0 on the current "g", "lbg", "ubg",
+ *                        "Araw", "grad", "P", "work"[0], slacks and multipliers; nothing is
+ *                        evaluated first
+ *   PL_IP_STAGE_INERTIA  one launch of k_ip_inertia (cap 8) on the current "ip_iflag", "ip_dwi",
+ *                        "P", "Ps"
+ *   PL_IP_STAGE_STEP     the rows and the objective at the current x, then k_ip_step with the
+ *                        line search and the update, on the current "ip_dx", "ip_jdx", "xa", "za",
+ *                        "rho", "ip_rh", slacks, multipliers and "ipinfo"
+ * pl_debug_get / pl_debug_set names that serve them: "work" ([batch][8], [0] = f), "ip_iflag"
+ * ([batch][4] ints as doubles), "info_done" ([batch], PlProbInfo::done as a double) and "ipinfo",
+ * [batch][PL_IPINFO_DOUBLES] with the fields in this order (ints as doubles):
+ *   0 mu, 1 theta_max, 2 theta_min, 3 err, 4 f, 5 alpha, 6 alpha_z, 7 viol_max, 8 iter,
+ *   9 status, 10 nfilt, 11 trials, 12 active, 13 ref_solves, 14 ref_last,
+ *   15 .. 78 filt[64] ((theta, phi) pairs), 79 .. 110 alphas[32] */
+#define PL_IP_STAGE_INIT 0
+#define PL_IP_STAGE_KKT 1
+#define PL_IP_STAGE_INERTIA 2
+#define PL_IP_STAGE_STEP 3
+#define PL_IPINFO_DOUBLES 111
+int pl_debug_ip_stage(pl_ocp* o, int stage, int arg);
 
 #ifdef __cplusplus
 }

@@ -1190,6 +1190,21 @@ extern "C" int pl_debug_ip_direction(pl_ocp* o, const double* S, const double* L
   return 0;
 }
 
+// Tests: one interior-point stage on the device buffers as they are (include/pinoloco.h).
+extern "C" int pl_debug_ip_stage(pl_ocp* o, int stage, int arg) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (!h->d.ipinfo) { pl_set_error("no interior-point state (pl_ocp_set_solver(o, PL_SOLVER_IP) first)"); return -1; }
+  if (stage == PL_IP_STAGE_KKT && (arg < 0 || arg > h->ip.max_iter)) {
+    pl_set_error("ip stage KKT: iteration %d outside [0, max_iter %d]", arg, h->ip.max_iter);
+    return -1;
+  }
+  if (enqueue_ip_stage(h, stage, arg) != 0) { pl_set_error("ip stage %d unknown", stage); return -1; }
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 extern "C" int pl_ocp_solve(pl_ocp* o, pl_stats* stats, double* phase_ms) {
   REQUIRE_DEVICE(o);
   if (o->h.solver == PL_SOLVER_IP) {
@@ -1959,13 +1974,79 @@ extern "C" int pl_ocp_sizes(const pl_ocp* o, long long* out) {
   return 0;
 }
 
+// The arrays that are not doubles on the device, passed as doubles (interior-point stage tests):
+// "ip_iflag" [B][4], "info_done" [B] (PlProbInfo::done) and "ipinfo" [B][PL_IPINFO_DOUBLES] in
+// the field order of include/pinoloco.h.  1: handled, 0: another name, < 0: error.
+static int debug_rw_records(pl_ocp* o, const char* name, double* out, const double* in, long long count) {
+  PlOcpHandle* h = &o->h;
+  const size_t B = h->B;
+  const int which = !strcmp(name, "ip_iflag") ? 0 : !strcmp(name, "info_done") ? 1 : !strcmp(name, "ipinfo") ? 2 : -1;
+  if (which < 0) return 0;
+  if (which != 1 && !h->d.ipinfo) { pl_set_error("array %s not allocated (set_solver first)", name); return -1; }
+  const size_t len = B * (which == 0 ? 4 : which == 1 ? 1 : PL_IPINFO_DOUBLES);
+  if ((size_t)count < len) { pl_set_error("buffer too small for %s (%zu)", name, len); return -1; }
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  if (which == 0) {
+    std::vector<int> F(4 * B);
+    if (out) {
+      PL_CHECK_HIP(hipMemcpy(F.data(), h->d.ip_iflag, F.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (size_t q = 0; q < F.size(); ++q) out[q] = F[q];
+    } else {
+      for (size_t q = 0; q < F.size(); ++q) F[q] = (int)in[q];
+      PL_CHECK_HIP(hipMemcpy(h->d.ip_iflag, F.data(), F.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    return 1;
+  }
+  if (which == 1) {
+    std::vector<PlProbInfo> info(B);
+    PL_CHECK_HIP(hipMemcpy(info.data(), h->d.info, B * sizeof(PlProbInfo), hipMemcpyDeviceToHost));
+    if (out) {
+      for (size_t b = 0; b < B; ++b) out[b] = info[b].done;
+    } else {
+      for (size_t b = 0; b < B; ++b) info[b].done = (int)in[b];
+      PL_CHECK_HIP(hipMemcpy(h->d.info, info.data(), B * sizeof(PlProbInfo), hipMemcpyHostToDevice));
+    }
+    return 1;
+  }
+  static_assert(PL_IPINFO_DOUBLES == 15 + 3 * PL_IP_MAXFILT, "ipinfo record (include/pinoloco.h)");
+  std::vector<PlIpInfo> ip(B);
+  PL_CHECK_HIP(hipMemcpy(ip.data(), h->d.ipinfo, B * sizeof(PlIpInfo), hipMemcpyDeviceToHost));
+  for (size_t b = 0; b < B; ++b) {
+    PlIpInfo& s = ip[b];
+    if (out) {
+      double* r = out + b * PL_IPINFO_DOUBLES;
+      const double head[15] = {s.mu, s.theta_max, s.theta_min, s.err, s.f, s.alpha, s.alpha_z, s.viol_max,
+                               (double)s.iter, (double)s.status, (double)s.nfilt, (double)s.trials,
+                               (double)s.active, (double)s.ref_solves, s.ref_last};
+      for (int q = 0; q < 15; ++q) r[q] = head[q];
+      for (int q = 0; q < 2 * PL_IP_MAXFILT; ++q) r[15 + q] = s.filt[q];
+      for (int q = 0; q < PL_IP_MAXFILT; ++q) r[15 + 2 * PL_IP_MAXFILT + q] = s.alphas[q];
+    } else {
+      const double* r = in + b * PL_IPINFO_DOUBLES;
+      s.mu = r[0]; s.theta_max = r[1]; s.theta_min = r[2]; s.err = r[3]; s.f = r[4]; s.alpha = r[5];
+      s.alpha_z = r[6]; s.viol_max = r[7];
+      s.iter = (int)r[8]; s.status = (int)r[9]; s.nfilt = (int)r[10]; s.trials = (int)r[11];
+      s.active = (int)r[12]; s.ref_solves = (int)r[13]; s.ref_last = r[14];
+      if (s.iter < 0 || s.iter >= PL_IP_MAXFILT || s.nfilt < 0 || s.nfilt > PL_IP_MAXFILT) {
+        pl_set_error("ipinfo: iter %d or nfilt %d outside the record", s.iter, s.nfilt);
+        return -1;
+      }
+      for (int q = 0; q < 2 * PL_IP_MAXFILT; ++q) s.filt[q] = r[15 + q];
+      for (int q = 0; q < PL_IP_MAXFILT; ++q) s.alphas[q] = r[15 + 2 * PL_IP_MAXFILT + q];
+    }
+  }
+  if (in) PL_CHECK_HIP(hipMemcpy(h->d.ipinfo, ip.data(), B * sizeof(PlIpInfo), hipMemcpyHostToDevice));
+  return 1;
+}
+
 // Debug / parity access to internal per-problem arrays (tests only).
 static int debug_rw(pl_ocp* o, const char* name, double* out, const double* in, long long count) {
   PlOcpHandle* h = &o->h;
   const size_t B = h->B;
+  if (const int rec = debug_rw_records(o, name, out, in, count)) return rec < 0 ? rec : 0;
   struct Item { const char* n; double* p; size_t len; } items[] = {
       {"Hlag", h->d.Hlag, h->d.Hlag ? B * (size_t)h->hl_stride : 0},
-      {"ip_dwi", h->d.ip_dwi, h->d.ip_dwi ? 2 * B : 0},
+      {"ip_dwi", h->d.ip_dwi, h->d.ip_dwi ? 2 * B : 0}, {"work", h->d.work, B * 8},
       {"As", h->d.As, B * h->nnz}, {"Araw", h->d.Araw, B * h->nnz}, {"qs", h->d.qs, B * h->n},
       {"ls", h->d.ls, B * h->m},   {"us", h->d.us, B * h->m},       {"rho", h->d.rho, B * h->m},
       {"D", h->d.D, B * h->n},     {"E", h->d.E, B * h->m},         {"cs", h->d.cs, B},

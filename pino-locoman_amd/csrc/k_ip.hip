@@ -922,3 +922,32 @@ void enqueue_ip_direction(PlOcpHandle* h) {
   PL_DISPATCH_DYN(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st, 1);
   h->set = saved;
 }
+
+// Stage tests (pl_debug_ip_stage): exactly one stage on the device buffers as they are.  INIT
+// and KKT evaluate nothing first, so the rows, the Jacobian and the iterate can be uploaded;
+// STEP evaluates the rows and the objective at d.x (what the solve's iteration has done by
+// then) and takes the direction (ip_dx, ip_jdx, xa, za) as it is.
+int enqueue_ip_stage(PlOcpHandle* h, int stage, int arg) {
+  const PlIpSettings st = h->ip;
+  switch (stage) {
+    case PL_IP_STAGE_INIT:
+      hipLaunchKernelGGL(k_ip_init, dim3(h->B), dim3(256), 0, h->stream, h->d, h->m, st, arg ? 1 : 0);
+      return 0;
+    case PL_IP_STAGE_KKT:
+      if (arg < 0) return -1;
+      hipLaunchKernelGGL(k_ip_kkt, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->nnz,
+                         std::max(h->ncpl_max, 1), arg, st);
+      h->admm_rho_rule = 0;
+      return 0;
+    case PL_IP_STAGE_INERTIA:
+      hipLaunchKernelGGL(k_ip_inertia, dim3(h->B), dim3(256), 0, h->stream, h->d, h->n, PL_IP_INERTIA_CAP);
+      return 0;
+    case PL_IP_STAGE_STEP:
+      launch_eval_values(h, h->d.x);
+      launch_objective(h);
+      PL_DISPATCH_DYN(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st,
+                      0);
+      return 0;
+  }
+  return -1;
+}

@@ -461,6 +461,7 @@ void launch_reset_iterates(PlOcpHandle* h);
 void launch_reset_prof(PlOcpHandle* h);
 void enqueue_ip(PlOcpHandle* h);
 void enqueue_ip_direction(PlOcpHandle* h);
+int enqueue_ip_stage(PlOcpHandle* h, int stage, int arg);  // pl_debug_ip_stage: -1 = unknown stage / bad arg
 
 #define PL_CHECK_HIP(expr)                                                        \
   do {                                                                            \

@@ -158,6 +158,7 @@ EXPORTS = {
     "pl_debug_admm": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_debug_qp_setup": (C.c_int, [C.c_void_p]),
     "pl_debug_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pl_debug_ip_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_dyn_create": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "pl_dyn_destroy": (None, [C.c_void_p]),
     "pl_dyn_sizes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip]),

@@ -451,6 +451,38 @@ class BatchedOCP:
         _lib.check(_lib.lib().pl_debug_check(self.h, int(bool(final)), int(bool(unscale))))
         return self.mpc_stats()
 
+    IP_STAGES = {"init": 0, "kkt": 1, "inertia": 2, "step": 3}
+    # the "ipinfo" record of debug / debug_set (include/pinoloco.h): scalar fields, then filt, alphas
+    IPINFO_FIELDS = ("mu", "theta_max", "theta_min", "err", "f", "alpha", "alpha_z", "viol_max", "iter", "status",
+                     "nfilt", "trials", "active", "ref_solves", "ref_last")
+    IPINFO_DOUBLES = 111
+
+    def debug_ip_stage(self, stage, arg=0):
+        """Stage tests: exactly one interior-point stage on the device buffers as they are
+        ("init": arg = warm; "kkt": arg = iteration k; "inertia": one launch; "step": rows and
+        objective at x, then the line search and the update on the uploaded direction)."""
+        _lib.check(_lib.lib().pl_debug_ip_stage(self.h, self.IP_STAGES[stage], int(arg)))
+
+    def debug_ipinfo(self):
+        """The per-problem interior-point records: {field: [batch]} plus "filt" [batch][32][2]
+        and "alphas" [batch][32]."""
+        B, k = self.batch, len(self.IPINFO_FIELDS)
+        rec = self.debug("ipinfo", B * self.IPINFO_DOUBLES).reshape(B, self.IPINFO_DOUBLES)
+        out = {nm: rec[:, q].copy() for q, nm in enumerate(self.IPINFO_FIELDS)}
+        out["filt"] = rec[:, k:k + 64].reshape(B, 32, 2).copy()
+        out["alphas"] = rec[:, k + 64:].copy()
+        return out
+
+    def debug_set_ipinfo(self, info):
+        """Uploads records shaped as debug_ipinfo returns them."""
+        B, k = self.batch, len(self.IPINFO_FIELDS)
+        rec = np.zeros((B, self.IPINFO_DOUBLES))
+        for q, nm in enumerate(self.IPINFO_FIELDS):
+            rec[:, q] = info[nm]
+        rec[:, k:k + 64] = np.asarray(info["filt"], dtype=np.float64).reshape(B, 64)
+        rec[:, k + 64:] = info["alphas"]
+        self.debug_set("ipinfo", rec)
+
     def lag_hess(self):
         """The interior point's Lagrangian Hessian blocks of the last Newton system (tests):
         [batch] list of csr n x n matrices (k_lag_hess, packed lower per node)."""
