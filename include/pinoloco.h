@@ -444,6 +444,63 @@ int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, const doubl
  * host synchronisation between them on the OSQP path.  A failing step ends the loop with its
  * error. */
 int pl_mpc_run(pl_ocp* o, int k0, int steps);
+
+/* Gait and command timelines: per problem, which gait the loop walks and which targets it tracks
+ * at every MPC step, decided on the device (robot.set_gait_sequence and set_tracking_targets
+ * between two iterations of run_mpc.py's loop, run_mpc.py:15-24).  Off by default, and then the
+ * gait / warm-start launch does exactly what it does without it.
+ *
+ * A problem's timeline is a list of keyframes sorted by k_start.  At step k the governing
+ * keyframe s is the last one with k_start <= k; before the first keyframe the first one governs
+ * (clamped).  The gait / warm-start launch of step k then writes into the problem's parameters
+ *   1. the commands: base_vel_des always, ext_force_des / arm_vel_des only where the OCP has the
+ *      external-force / arm frame.  With ramp == 0, with no keyframe s + 1 or with k < k_start_s
+ *      they are keyframe s's, bit for bit; otherwise a = (double)(k - k_s) / (double)(k_{s+1} - k_s)
+ *      and c = c_s + a (c_{s+1} - c_s) per component;
+ *   2. n_contacts and swing_period of keyframe s's gait: trot 2, period / 2; walk 3, period / 4;
+ *      stand 4, period (GaitSequence.__init__, utils/gait_sequence.py:11-21);
+ *   3. the contact and swing schedules of the whole horizon for keyframe s's gait and period at
+ *      the clock t = (t0[b] + k dt_min) + t_shift_s, the bracket rounded once (a fused
+ *      multiply-add, as the device has always computed it).  One gait per solve: it changes between
+ *      solves, never inside a horizon;
+ *   4. for k > 0 the force warm start, f_des masked by the new schedule, with the new n_contacts.
+ * While a timeline is set, a pl_ocp_set_params of the command fields, n_contacts or swing_period
+ * is overwritten at the next step.  The keyframes live in device buffers that only that launch
+ * reads, outside the captured step: setting, changing or clearing a timeline never re-captures.
+ * Both solvers and every plant mode work alike. */
+typedef struct {
+  int k_start;              /* first MPC step this keyframe governs */
+  int gait_type;            /* 0 trot, 1 walk, 2 stand (as pl_ocp_desc.gait_type) */
+  int ramp;                 /* 0: hold this keyframe's commands; 1: go linearly to the next keyframe's */
+  int pad;
+  double gait_period;       /* > 0 */
+  double t_shift;           /* added to the gait clock while this keyframe governs (phase alignment at a switch) */
+  double base_vel_des[6];
+  double ext_force_des[3];  /* ignored where the OCP has no external-force frame */
+  double arm_vel_des[3];    /* ignored where it has no arm frame */
+} pl_mpc_keyframe;
+#define PL_MPC_MAX_KEYFRAMES 64
+/* keys [batch][n_key], count [batch] valid keyframes of each problem (NULL: n_key each); entries
+ * past a problem's count are never read.  keys == NULL switches the timeline off.  Refused before
+ * any device work, with the problem and keyframe in pl_last_error, and leaving a set timeline as
+ * it is: n_key outside [1, 64], a count outside [1, n_key], a negative k_start or k_start not
+ * strictly increasing within a problem's count, a gait_type outside 0..2, a gait_period that is
+ * not finite and positive, a non-finite t_shift or command, a ramp other than 0 or 1, a handle
+ * without a device. */
+int pl_mpc_set_timeline(pl_ocp* o, int n_key, const pl_mpc_keyframe* keys, const int* count);
+int pl_mpc_get_timeline(const pl_ocp* o, int* on, int* n_key);
+/* What the last gait / warm-start launch used, per problem: the governing keyframe's index, gait
+ * type and period, and the 12 commands it evaluated (base_vel_des, ext_force_des, arm_vel_des;
+ * all 12, also those the OCP has no parameter for).  Written by the kernel, read through the
+ * pinned staging buffer; any pointer may be NULL.  Needs a timeline. */
+int pl_mpc_timeline_state(pl_ocp* o, int* seg /*[batch]*/, int* gait_type /*[batch]*/, double* gait_period /*[batch]*/,
+                          double* commands /*[batch][12]*/);
+/* One problem's prepare step on the host, the code the kernel runs: steps 1-3 above into p [np]
+ * for step k, gait offset t0 and this problem's `count` keyframes, and, for k > 0 with x [n]
+ * given, step 4 into x.  *seg (may be NULL): the governing keyframe.  x_init is not touched.
+ * Validates the keyframes as pl_mpc_set_timeline does.  Works on a handle without a device. */
+int pl_mpc_timeline_host(const pl_ocp* o, int k, double t0, const pl_mpc_keyframe* keys, int count, double* p,
+                         double* x, int* seg);
 int pl_ocp_sync(pl_ocp* o);
 
 /* Host-side state maps, x = [q, v], dx = [dq, dv]
@@ -598,6 +655,9 @@ int pl_debug_consts(const pl_ocp* o, void* model_out, void* oc_out, int* sizes);
 int pl_debug_admm(pl_ocp* o, int niter, int reset);
 /* Ruiz scaling + scaled data alone on the raw arrays as they are (no evaluation, no factor). */
 int pl_debug_qp_setup(pl_ocp* o);
+/* The gait / warm-start launch of MPC step k alone (x_init, push window, timeline, schedule,
+ * warm start), then a synchronise: p and x can be read before any solve overwrites the iterate. */
+int pl_debug_mpc_prepare(pl_ocp* o, int k);
 /* One termination check on the current iterates and scaled data, then (unscale) the step
  * write-back; read status / pri_res / dua_res with pl_mpc_get_stats. */
 int pl_debug_check(pl_ocp* o, int final_check, int unscale);

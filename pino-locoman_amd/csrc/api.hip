@@ -11,6 +11,7 @@
 #include "record.h"
 #include "retract.h"
 #include "rho_adapt.h"
+#include "timeline.h"
 
 #include <map>
 
@@ -26,7 +27,8 @@ void pl_set_error(const char* fmt, ...) {
 
 
 extern "C" const char* pl_last_error(void) { return g_err; }
-extern "C" int pl_version(void) { return 1; }
+// 2: pl_mpc_set_timeline and its siblings, pl_debug_mpc_prepare
+extern "C" int pl_version(void) { return 2; }
 
 // Build provenance: build.py passes the sha256 of csrc/* + include/*.h (PL_SRC_SHA), so a
 // caller can tell which sources a pushed binary was built from (bench.py prints it,
@@ -434,6 +436,9 @@ extern "C" void pl_ocp_destroy(pl_ocp* o) {
     if (o->mpc_graph) hipGraphExecDestroy(o->mpc_graph);
     if (o->dl_host) hipHostFree(o->dl_host);
     if (o->h.rec_log) hipFree(o->h.rec_log);
+    if (o->h.tl_keys) hipFree(o->h.tl_keys);
+    if (o->h.tl_count) hipFree(o->h.tl_count);
+    if (o->h.tl_state) hipFree(o->h.tl_state);
     if (o->rt_dev) hipFree(o->rt_dev);
     if (o->rt_host) hipHostFree(o->rt_host);
     hipStreamDestroy(o->h.stream);
@@ -1781,6 +1786,173 @@ extern "C" int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, 
   PL_CHECK_HIP(hipMemcpyAsync(h->push_w, wrench, B * 6 * 8, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->push_on = 1;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Gait and command timelines (timeline.h): keyframes per problem in device buffers that
+// k_mpc_prepare alone reads.  Their state sits behind the MPC graph key (state.h), like the push
+// schedule's, and that launch runs outside the captured step.
+static_assert(sizeof(pl_mpc_keyframe) == sizeof(PlKeyframe) && sizeof(PlKeyframe) == 128,
+              "pl_mpc_keyframe and PlKeyframe are one layout");
+static_assert(PL_MPC_MAX_KEYFRAMES == PL_TL_MAXKEY, "one keyframe limit");
+
+// one problem's keyframes [0, count): every refusal of pl_mpc_set_timeline below the counts
+static int timeline_check(const char* who, size_t b, const pl_mpc_keyframe* keys, int count) {
+  for (int j = 0; j < count; ++j) {
+    const pl_mpc_keyframe& K = keys[j];
+    if (K.k_start < 0) {
+      pl_set_error("%s: problem %zu, keyframe %d: k_start %d is negative", who, b, j, K.k_start);
+      return -1;
+    }
+    if (j > 0 && K.k_start <= keys[j - 1].k_start) {
+      pl_set_error("%s: problem %zu, keyframe %d: k_start %d does not increase (keyframe %d starts at %d)", who, b, j,
+                   K.k_start, j - 1, keys[j - 1].k_start);
+      return -1;
+    }
+    if (K.gait_type < 0 || K.gait_type > 2) {
+      pl_set_error("%s: problem %zu, keyframe %d: gait_type %d outside 0..2", who, b, j, K.gait_type);
+      return -1;
+    }
+    if (!(std::isfinite(K.gait_period) && K.gait_period > 0.0)) {
+      pl_set_error("%s: problem %zu, keyframe %d: gait_period %g is not finite and positive", who, b, j, K.gait_period);
+      return -1;
+    }
+    if (!std::isfinite(K.t_shift)) {
+      pl_set_error("%s: problem %zu, keyframe %d: t_shift %g is not finite", who, b, j, K.t_shift);
+      return -1;
+    }
+    if (K.ramp != 0 && K.ramp != 1) {
+      pl_set_error("%s: problem %zu, keyframe %d: ramp %d is neither 0 nor 1", who, b, j, K.ramp);
+      return -1;
+    }
+    const double* c = K.base_vel_des;  // the 12 commands are contiguous (the layout assert above)
+    for (int e = 0; e < PL_TL_NCMD; ++e)
+      if (!std::isfinite(c[e])) {
+        pl_set_error("%s: problem %zu, keyframe %d: command %d (%s[%d]) = %g is not finite", who, b, j, e,
+                     e < 6 ? "base_vel_des" : e < 9 ? "ext_force_des" : "arm_vel_des", e < 6 ? e : e < 9 ? e - 6 : e - 9,
+                     c[e]);
+        return -1;
+      }
+  }
+  return 0;
+}
+
+extern "C" int pl_mpc_set_timeline(pl_ocp* o, int n_key, const pl_mpc_keyframe* keys, const int* count) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  const size_t B = o->h.B;
+  if (keys) {
+    if (n_key < 1 || n_key > PL_TL_MAXKEY) {
+      pl_set_error("pl_mpc_set_timeline: n_key %d outside [1, %d]", n_key, PL_TL_MAXKEY);
+      return -1;
+    }
+    for (size_t b = 0; b < B; ++b) {
+      const int cnt = count ? count[b] : n_key;
+      if (cnt < 1 || cnt > n_key) {
+        pl_set_error("pl_mpc_set_timeline: problem %zu: count %d outside [1, %d]", b, cnt, n_key);
+        return -1;
+      }
+      if (timeline_check("pl_mpc_set_timeline", b, keys + b * n_key, cnt)) return -1;
+    }
+  }
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (!keys) {
+    h->tl_on = 0;
+    return 0;
+  }
+  if (h->tl_nkey != n_key) {  // another stride: the keyframe buffer is reallocated
+    PL_CHECK_HIP(hipStreamSynchronize(h->stream));  // an earlier prepare launch may still read the old one
+    h->tl_on = 0;
+    if (h->tl_keys) hipFree(h->tl_keys);
+    h->tl_keys = nullptr;
+    h->tl_nkey = 0;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, B * n_key * sizeof(PlKeyframe));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      pl_set_error("pl_mpc_set_timeline: hipMalloc(%zu bytes): %s", B * n_key * sizeof(PlKeyframe), hipGetErrorString(e));
+      return -2;
+    }
+    h->tl_keys = (PlKeyframe*)q;
+    h->tl_nkey = n_key;
+  }
+  if (!h->tl_count) {
+    void *qc = nullptr, *qs = nullptr;
+    if (hipMalloc(&qc, B * sizeof(int)) != hipSuccess || hipMalloc(&qs, B * sizeof(PlTimelineState)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (qc) hipFree(qc);
+      pl_set_error("pl_mpc_set_timeline: hipMalloc of the count / state buffers failed");
+      return -2;
+    }
+    h->tl_count = (int*)qc;
+    h->tl_state = (PlTimelineState*)qs;
+    PL_CHECK_HIP(hipMemsetAsync(h->tl_state, 0, B * sizeof(PlTimelineState), h->stream));
+  }
+  // the keyframes each problem owns, the padding zeroed: nothing the caller left there travels
+  std::vector<PlKeyframe> hk(B * n_key);
+  std::vector<int> hc(B);
+  memset(hk.data(), 0, hk.size() * sizeof(PlKeyframe));
+  for (size_t b = 0; b < B; ++b) {
+    hc[b] = count ? count[b] : n_key;
+    memcpy(hk.data() + b * n_key, keys + b * n_key, (size_t)hc[b] * sizeof(PlKeyframe));
+  }
+  PL_CHECK_HIP(hipMemcpyAsync(h->tl_keys, hk.data(), hk.size() * sizeof(PlKeyframe), hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipMemcpyAsync(h->tl_count, hc.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));  // hk, hc are read until the copies have run
+  h->tl_on = 1;
+  return 0;
+}
+
+extern "C" int pl_mpc_get_timeline(const pl_ocp* o, int* on, int* n_key) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (on) *on = o->h.tl_on;
+  if (n_key) *n_key = o->h.tl_on ? o->h.tl_nkey : 0;
+  return 0;
+}
+
+extern "C" int pl_mpc_timeline_state(pl_ocp* o, int* seg, int* gait_type, double* gait_period, double* commands) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (!h->tl_on) { pl_set_error("pl_mpc_timeline_state: no timeline is set (pl_mpc_set_timeline)"); return -1; }
+  const size_t B = h->B, bytes = B * sizeof(PlTimelineState);
+  if (stage_reserve(o, bytes)) return -2;
+  PL_CHECK_HIP(hipMemcpyAsync(o->dl_host, h->tl_state, bytes, hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  const PlTimelineState* st = (const PlTimelineState*)o->dl_host;
+  for (size_t b = 0; b < B; ++b) {
+    if (seg) seg[b] = st[b].seg;
+    if (gait_type) gait_type[b] = st[b].gait_type;
+    if (gait_period) gait_period[b] = st[b].gait_period;
+    if (commands) memcpy(commands + b * PL_TL_NCMD, st[b].cmd, sizeof(st[b].cmd));
+  }
+  return 0;
+}
+
+extern "C" int pl_mpc_timeline_host(const pl_ocp* o, int k, double t0, const pl_mpc_keyframe* keys, int count, double* p,
+                                    double* x, int* seg) {
+  if (!o || !keys || !p) { pl_set_error("pl_mpc_timeline_host: null argument"); return -1; }
+  if (count < 1 || count > PL_TL_MAXKEY) {
+    pl_set_error("pl_mpc_timeline_host: count %d outside [1, %d]", count, PL_TL_MAXKEY);
+    return -1;
+  }
+  if (!std::isfinite(t0)) { pl_set_error("pl_mpc_timeline_host: t0 = %g is not finite", t0); return -1; }
+  if (timeline_check("pl_mpc_timeline_host", 0, keys, count)) return -1;
+  const PlOcpHandle& h = o->h;
+  std::vector<PlKeyframe> hk(count);  // exactly the problem's keyframes
+  memcpy(hk.data(), keys, (size_t)count * sizeof(PlKeyframe));
+  PlTimelineState st;
+  pl::timeline_prepare_host(h.model, h.oc, o->nodes.data(), k, t0, hk.data(), count, p, x, &st);
+  if (seg) *seg = st.seg;
+  return 0;
+}
+
+extern "C" int pl_debug_mpc_prepare(pl_ocp* o, int k) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  launch_mpc_prepare(h, k);
+  PL_CHECK_HIP(hipGetLastError());
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
 

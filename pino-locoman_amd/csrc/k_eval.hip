@@ -9,6 +9,7 @@
 // writing the column's entries of the fixed sparsity pattern (CSC order inside the node).
 #include "dyn.h"
 #include "eval_common.h"
+#include "timeline.h"
 
 using pl::VecIn;
 
@@ -413,9 +414,14 @@ void launch_line_search(PlOcpHandle* h) {
 // noise (pl_mpc_set_disturbance, null: none): the MPC plans from the measured state
 // x_init = state_integrate(x_state, noise_b), the "add noise to x_init" of run_mpc.py:79-82;
 // x_state stays the true state.
+// keys (pl_mpc_set_timeline, null: none): [B][n_key] keyframes, count [B] of them valid, tls [B]
+// what this launch used.  With a timeline the problem's commands, gait scalars and schedule come
+// from its governing keyframe (timeline.h) instead of the handle's one gait; the warm start below
+// then sees the new n_contacts.
 __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n, int np, int nx, int gait_type,
                                                     double period, double swing_period, const double* noise,
-                                                    const int* push_k, const double* push_w) {
+                                                    const int* push_k, const double* push_w, const PlKeyframe* keys,
+                                                    int n_key, const int* count, PlTimelineState* tls) {
   const int b = blockIdx.x;
   const PlOcpConst& O = *d.oc;
   const PlModel& M = *d.model;
@@ -442,8 +448,32 @@ __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n
       for (int j = 0; j < O.nv; ++j) xi[O.nq + j] = xs[O.nq + j] + nb[O.nv + j];
     }
   }
+  double t_shift = 0.0;
+  if (keys) {
+    const PlKeyframe* kb = keys + (size_t)b * n_key;
+    const int cnt = count[b];
+    const int s = pl::tl_segment(kb, cnt, k);  // uniform over the workgroup
+    if (threadIdx.x < PL_TL_NCMD) {            // one command component per lane
+      const int j = threadIdx.x;
+      const double c = pl::tl_command(kb, cnt, s, k, j);
+      if (pl::tl_has_command(O, j)) p[pl::tl_command_off(O, j)] = c;
+      tls[b].cmd[j] = c;
+    }
+    gait_type = kb[s].gait_type;
+    period = kb[s].gait_period;
+    swing_period = pl::tl_swing_period(gait_type, period);
+    t_shift = kb[s].t_shift;
+    if (threadIdx.x == 0) {
+      p[O.P.n_contacts] = pl::tl_n_contacts(gait_type);
+      p[O.P.swing_period] = swing_period;
+      tls[b].seg = s;
+      tls[b].gait_type = gait_type;
+      tls[b].gait_period = period;
+    }
+  }
   if (threadIdx.x == 0) {
-    double t = d.t0[b] + k * p[O.P.dt_min];
+    double t = pl::mpc_clock(d.t0[b], k, p[O.P.dt_min]);
+    if (keys) t += t_shift;
     pl::gait_schedule(O, gait_type, period, swing_period, t, p, p + O.P.contact, p + O.P.swing);
   }
   __syncthreads();
@@ -452,11 +482,7 @@ __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n
   const int fo = pl::u_force_off(O);
   for (int idx = threadIdx.x; idx < N * O.nf; idx += blockDim.x) {  // (node, force component) on the lanes
     const int i = idx / O.nf, c = idx - i * O.nf;
-    const int base = d.nodes[i].x_off + O.ndx + fo;
-    int foot = c / 3;
-    double fd = pl::f_des_comp(M, O, p, c);
-    if (foot < 4 && p[O.P.contact + 4 * i + foot] == 0.0) fd = 0.0;
-    x[base + c] = fd;
+    x[d.nodes[i].x_off + O.ndx + fo + c] = pl::warm_force(M, O, p, i, c);
   }
 }
 
@@ -486,7 +512,8 @@ void launch_mpc_prepare(PlOcpHandle* h, int k) {
   hipLaunchKernelGGL(k_mpc_prepare, dim3(h->B), dim3(64), 0, h->stream, h->d, k, h->N, h->n, h->np, h->nx,
                      h->gait_type, h->gait_period, h->swing_period,
                      h->plant_noise_on ? (const double*)h->d.plant_noise : nullptr,
-                     h->push_on ? (const int*)h->push_k : nullptr, (const double*)h->push_w);
+                     h->push_on ? (const int*)h->push_k : nullptr, (const double*)h->push_w,
+                     h->tl_on ? (const PlKeyframe*)h->tl_keys : nullptr, h->tl_nkey, (const int*)h->tl_count, h->tl_state);
 }
 
 void launch_mpc_finish(PlOcpHandle* h) {

@@ -410,6 +410,14 @@ struct PlOcpHandle {
   int push_on;                 // 1 while pl_mpc_set_push holds a schedule: k_mpc_prepare writes d.plant_w
   int* push_k;                 // [2][B]: k_start, k_end
   double* push_w;              // [B][6]
+  // Gait and command timelines (pl_mpc_set_timeline, timeline.h): read by k_mpc_prepare alone, so
+  // outside the key like the push schedule; setting, changing or clearing one never re-captures.
+  // The three buffers are the handle's own allocations, reallocated when n_key changes.
+  int tl_on;                         // 1 while a timeline is set
+  int tl_nkey;                       // keyframe slots per problem of tl_keys
+  struct PlKeyframe* tl_keys;        // [B][tl_nkey]
+  int* tl_count;                     // [B] valid keyframes of each problem
+  struct PlTimelineState* tl_state;  // [B] what the last prepare launch used
 };
 
 // ---- kernel launchers (defined in the k_*.hip translation units)

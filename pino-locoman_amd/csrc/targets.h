@@ -50,13 +50,22 @@ PL_HD double u_des(const PlModel& M, const PlOcpConst& O, const double* p, int k
   return 0.0;
 }
 
+// t + dt_i with dt_i = dt_min gamma^i as node_dt has it, the product and the sum rounded once.
+// The device build has always contracted the two into one fused multiply-add; stating the
+// fusion gives the host build (pl_mpc_timeline_host) the same bits.
+PL_HD double time_after_node(const PlOcpConst& O, const double* p, int i, double t) {
+  double dt_min = p[O.P.dt_min], dt_max = p[O.P.dt_max];
+  double gamma = pow(dt_max / dt_min, 1.0 / (double)(O.N - 1));
+  return __builtin_fma(dt_min, pow(gamma, (double)i), t);
+}
+
 // Gait schedule (utils/gait_sequence.py:26-77) for one problem.
 PL_HD void gait_schedule(const PlOcpConst& O, int gait_type, double period, double swing_period, double t_cur,
                               const double* p, double* contact, double* swing) {
   const int N = O.N;
   double t = t_cur;
   for (int i = 0; i < N; ++i) {
-    if (i > 0) t += pl::node_dt(O, p, i - 1);
+    if (i > 0) t = time_after_node(O, p, i - 1, t);
     for (int f = 0; f < 4; ++f) {
       contact[4 * i + f] = 1.0;
       swing[4 * i + f] = 0.0;

@@ -75,6 +75,20 @@ class MpcMetrics(C.Structure):
                 ("max_dz", C.c_double), ("min_cz", C.c_double), ("max_viol", C.c_double)]
 
 
+class Keyframe(C.Structure):
+    """pl_mpc_keyframe (include/pinoloco.h)."""
+    _fields_ = [("k_start", C.c_int), ("gait_type", C.c_int), ("ramp", C.c_int), ("pad", C.c_int),
+                ("gait_period", C.c_double), ("t_shift", C.c_double), ("base_vel_des", C.c_double * 6),
+                ("ext_force_des", C.c_double * 3), ("arm_vel_des", C.c_double * 3)]
+
+
+# the same record as a numpy structured dtype: an array [batch][n_key] of it is what
+# BatchedOCP.mpc_set_timeline uploads
+timeline_dtype = np.dtype([("k_start", np.int32), ("gait_type", np.int32), ("ramp", np.int32), ("pad", np.int32),
+                           ("gait_period", np.float64), ("t_shift", np.float64), ("base_vel_des", np.float64, (6,)),
+                           ("ext_force_des", np.float64, (3,)), ("arm_vel_des", np.float64, (3,))])
+assert timeline_dtype.itemsize == C.sizeof(Keyframe) == 128
+
 _llp = C.POINTER(C.c_longlong)
 
 EXPORTS = {
@@ -145,6 +159,10 @@ EXPORTS = {
                                      _dp, _dp, _llp, _dp, C.POINTER(MpcMetrics)]),
     "pl_mpc_set_push": (C.c_int, [C.c_void_p, _ip, _ip, _dp]),
     "pl_mpc_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pl_mpc_set_timeline": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Keyframe), _ip]),
+    "pl_mpc_get_timeline": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "pl_mpc_timeline_state": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp]),
+    "pl_mpc_timeline_host": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(Keyframe), C.c_int, _dp, _dp, _ip]),
     "pl_ocp_sync": (C.c_int, [C.c_void_p]),
     "pl_state_integrate": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "pl_state_difference": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -157,6 +175,7 @@ EXPORTS = {
     "pl_debug_nodes": (C.c_int, [C.c_void_p, _ip]),
     "pl_debug_admm": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_debug_qp_setup": (C.c_int, [C.c_void_p]),
+    "pl_debug_mpc_prepare": (C.c_int, [C.c_void_p, C.c_int]),
     "pl_debug_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_debug_ip_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pl_dyn_create": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

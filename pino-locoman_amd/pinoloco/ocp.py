@@ -737,6 +737,116 @@ class BatchedOCP:
         """mpc_step(k0) ... mpc_step(k0 + steps - 1), enqueued back to back (pl_mpc_run)."""
         _lib.check(_lib.lib().pl_mpc_run(self.h, int(k0), int(steps)))
 
+    # ---------------------------------------------------------------- gait and command timelines
+    KEYFRAME_FIELDS = ("k_start", "gait_type", "ramp", "gait_period", "t_shift", "base_vel_des", "ext_force_des",
+                       "arm_vel_des")
+
+    @staticmethod
+    def keyframe(k_start, gait="trot", gait_period=0.8, base_vel_des=(0, 0, 0, 0, 0, 0), ext_force_des=(0, 0, 0),
+                 arm_vel_des=(0, 0, 0), ramp=False, t_shift=0.0):
+        """One keyframe as a dict (gait: a name of GAIT_CODES or its code)."""
+        return dict(k_start=k_start, gait_type=gait, gait_period=gait_period, ramp=ramp, t_shift=t_shift,
+                    base_vel_des=base_vel_des, ext_force_des=ext_force_des, arm_vel_des=arm_vel_des)
+
+    def _keyframes(self, keys, problems, count=None):
+        """(array [problems][n_key] of _lib.timeline_dtype, count [problems] int32) from a structured
+        array of that shape or from one list of keyframe dicts per problem (padded here)."""
+        if isinstance(keys, np.ndarray):
+            if keys.dtype != _lib.timeline_dtype or keys.ndim != 2 or keys.shape[0] != problems:
+                raise _lib.PinolocoError(f"keys has dtype {keys.dtype} and shape {keys.shape}, expected "
+                                         f"timeline_dtype and ({problems}, n_key)")
+            arr = np.ascontiguousarray(keys)
+            cnt = self._per_problem(arr.shape[1] if count is None else count, "count", problems, dtype=np.int32)
+            return arr, np.ascontiguousarray(cnt)
+        if count is not None:
+            raise _lib.PinolocoError("count goes with a structured array; lists of keyframes carry their own length")
+        keys = list(keys)
+        if len(keys) != problems or any(isinstance(kf, dict) for kf in keys):
+            raise _lib.PinolocoError(f"keys: expected {problems} lists of keyframes, one per problem")
+        cnt = np.array([len(kf) for kf in keys], dtype=np.int32)
+        arr = np.zeros((problems, max(int(cnt.max()), 1)), dtype=_lib.timeline_dtype)
+        for b, kfs in enumerate(keys):
+            for j, kf in enumerate(kfs):
+                unknown = sorted(set(kf) - set(self.KEYFRAME_FIELDS) - {"gait"})
+                if unknown or "k_start" not in kf:
+                    raise _lib.PinolocoError(f"keyframe {j} of problem {b}: unknown fields {unknown} or no k_start "
+                                             f"(fields: {self.KEYFRAME_FIELDS})")
+                g = kf.get("gait_type", kf.get("gait", "trot"))
+                if isinstance(g, str):
+                    if g not in GAIT_CODES:
+                        raise _lib.PinolocoError(f"keyframe {j} of problem {b}: gait {g} unknown "
+                                                 f"(choose from {sorted(GAIT_CODES)})")
+                    g = GAIT_CODES[g]
+                rec = arr[b, j]
+                rec["k_start"], rec["gait_type"], rec["ramp"] = int(kf["k_start"]), int(g), int(kf.get("ramp", 0))
+                rec["gait_period"], rec["t_shift"] = float(kf.get("gait_period", 0.8)), float(kf.get("t_shift", 0.0))
+                for name, width in (("base_vel_des", 6), ("ext_force_des", 3), ("arm_vel_des", 3)):
+                    v = np.asarray(kf.get(name, np.zeros(width)), dtype=np.float64)
+                    if v.shape != (width,):
+                        raise _lib.PinolocoError(f"keyframe {j} of problem {b}: {name} has shape {v.shape}, "
+                                                 f"expected {(width,)}")
+                    rec[name] = v
+        return arr, cnt
+
+    def mpc_set_timeline(self, keys, count=None):
+        """Per-problem gait and command timelines (pl_mpc_set_timeline): at MPC step k problem b walks
+        the gait and tracks the commands of its governing keyframe, the last one with k_start <= k
+        (the first one before that); ramp goes linearly to the next keyframe's commands.  keys: a
+        structured array [batch][n_key] of _lib.timeline_dtype with count (a scalar or [batch],
+        default n_key; entries past it are never read), or one list of keyframe dicts per problem
+        (BatchedOCP.keyframe).  None switches the timeline off.  While one is set, the command
+        fields, n_contacts and swing_period of set_params are overwritten at the next step.  Never
+        re-captures the step's graph."""
+        if keys is None:
+            _lib.check(_lib.lib().pl_mpc_set_timeline(self.h, 0, None, None))
+            return
+        arr, cnt = self._keyframes(keys, self.batch, count)
+        _lib.check(_lib.lib().pl_mpc_set_timeline(self.h, arr.shape[1], arr.ctypes.data_as(C.POINTER(_lib.Keyframe)),
+                                                  _lib.iptr(cnt)))
+
+    def mpc_get_timeline(self):
+        """{"on": bool, "n_key": keyframe slots per problem (0 while off)}."""
+        on, nk = C.c_int(), C.c_int()
+        _lib.check(_lib.lib().pl_mpc_get_timeline(self.h, C.byref(on), C.byref(nk)))
+        return {"on": bool(on.value), "n_key": nk.value}
+
+    def mpc_timeline_state(self):
+        """What the last gait / warm-start launch used, per problem: {"seg", "gait_type", "gait_period"
+        [batch], "commands" [batch][12] (base_vel_des, ext_force_des, arm_vel_des)}."""
+        seg, gt = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32)
+        per, cmd = np.zeros(self.batch), np.zeros((self.batch, 12))
+        _lib.check(_lib.lib().pl_mpc_timeline_state(self.h, _lib.iptr(seg), _lib.iptr(gt), _lib.dptr(per), _lib.dptr(cmd)))
+        return {"seg": seg, "gait_type": gt, "gait_period": per, "commands": cmd}
+
+    def mpc_timeline_host(self, k, t0, keys, p, x=None, count=None):
+        """One problem's prepare step on the host, the code the kernel runs (pl_mpc_timeline_host):
+        keys, one problem's keyframes (a list of dicts, or a structured array [n_key] with count);
+        p [np] the parameters before, x [n] the iterate before (None: no warm start).  Returns
+        (p, x, seg): copies with the commands, gait scalars and schedule of step k written and,
+        for k > 0, the masked force warm start.  Needs no device."""
+        if isinstance(keys, np.ndarray):
+            keys = keys.reshape(1, -1)
+        else:
+            keys = [list(keys)]
+        arr, cnt = self._keyframes(keys, 1, count)
+        p = np.array(p, dtype=np.float64)
+        if p.shape != (self.np,):
+            raise _lib.PinolocoError(f"p has shape {p.shape}, expected {(self.np,)}")
+        if x is not None:
+            x = np.array(x, dtype=np.float64)
+            if x.shape != (self.n,):
+                raise _lib.PinolocoError(f"x has shape {x.shape}, expected {(self.n,)}")
+        seg = C.c_int(-1)
+        _lib.check(_lib.lib().pl_mpc_timeline_host(self.h, int(k), float(t0), arr.ctypes.data_as(C.POINTER(_lib.Keyframe)),
+                                                   int(cnt[0]), _lib.dptr(p), None if x is None else _lib.dptr(x),
+                                                   C.byref(seg)))
+        return p, x, seg.value
+
+    def debug_mpc_prepare(self, k):
+        """Stage tests: the gait / warm-start launch of MPC step k alone, then a synchronise;
+        get_params() and get_x() then show what the solve of step k would start from."""
+        _lib.check(_lib.lib().pl_debug_mpc_prepare(self.h, int(k)))
+
     def mpc_record_host(self, steps, z_ref, capacity=0, every=1, dz_tol=None, cz_min=None):
         """One problem's record steps on the host, the code the device runs (pl_mpc_record_host).
         steps: a list of dicts with k, x_init [nx], u0 [nu_0], stats (a dict of LOG_STATS), x_state

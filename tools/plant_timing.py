@@ -9,7 +9,9 @@ Two halves, because a kernel's own time comes from the profiler's kernel trace, 
       --contact adds the ground contact and joint PD of mpc_set_contact (k_plant's contact
       instantiation; profiles/plant/plant_contact_timing.json).  --log switches the rollout log on
       (mpc_log_start, one slot per step), so that every step also dispatches k_mpc_record
-      (profiles/plant/record_timing.json).
+      (profiles/plant/record_timing.json).  --timeline sets a three-keyframe timeline per problem
+      (mpc_set_timeline: trot with a velocity ramp, then walk), so that k_mpc_prepare evaluates it at
+      every step (profiles/plant/timeline_timing.json, parsed with @k_mpc_prepare).
   python tools/plant_timing.py parse LABEL[@KERNEL]=DIR [LABEL[@KERNEL]=DIR ...] [--out FILE]
       per label the median / min / max duration of the last 10 k_plant or k_mpc_finish dispatches
       of DIR's *kernel_trace.csv, as one JSON; @KERNEL picks the dispatches whose name contains
@@ -59,11 +61,18 @@ def run(args):
         bo.mpc_set_contact(c, bo.ground_under_feet(XS, args.penetration))
     if args.log:
         bo.mpc_log_start(capacity=WARM + STEPS, dz_tol=0.1, cz_min=0.5)
+    if args.timeline:
+        vx = P[:, lay.poff["base_vel_des"][0]]
+        kf = BatchedOCP.keyframe
+        bo.mpc_set_timeline([[kf(0, "trot", 0.8, [0, 0, 0, 0, 0, 0], ramp=True), kf(8, "trot", 0.8, [v, 0, 0, 0, 0, 0]),
+                              kf(11, "walk", 0.6, [0.5 * v, 0, 0, 0, 0, 0], t_shift=0.05)] for v in vx])
     for k in range(WARM + STEPS):
         bo.mpc_step(k)
     xs = bo.mpc_state()
     out = {"mode": args.mode, "substeps": args.substeps, "contact": bool(args.contact), "shape": args.shape,
            "lib": _lib.LIB_PATH, "lib_src_sha256": _lib.build_sha(), "finite": bool(np.all(np.isfinite(xs)))}
+    if args.timeline:
+        out["timeline_last_segment"] = sorted(set(bo.mpc_timeline_state()["seg"].tolist()))
     if args.log:
         sz = bo.mpc_log_sizes()
         out["log"] = {k: sz[k] for k in ("row", "recorded", "dropped")}
@@ -112,6 +121,7 @@ r.add_argument("--mode", default="aba", choices=["aba", "nominal"])
 r.add_argument("--substeps", type=int, default=1)
 r.add_argument("--contact", action="store_true", help="ground contact and joint PD (mpc_set_contact), aba only")
 r.add_argument("--log", action="store_true", help="the rollout log on: k_mpc_record after every step")
+r.add_argument("--timeline", action="store_true", help="a gait and command timeline on: k_mpc_prepare evaluates it")
 r.add_argument("--penetration", type=float, default=0.05)
 r.add_argument("--zeta", type=float, default=0.05)
 r.add_argument("shape", nargs="*", default=["b2g", "whole_body_rnea", "50", "1024"])
