@@ -59,21 +59,6 @@ __device__ __forceinline__ void wsync() {
 
 // sum_{k0 <= k < k1} f(k), 8 clamped independent reads per round (branch-free within a
 // round, so the LDS reads of a round issue back to back)
-// sum_{k0 <= k < k1} p[k * stride], U reads per round; reads past k1 go to a zero slot
-// (an index select instead of a select on the double)
-template <int U = 8>
-__device__ __forceinline__ double lds_sum(const double* p, int k0, int k1, int stride, const double* zero) {
-  double acc = 0.0;
-  for (int b = k0; b < k1; b += U) {
-    double t[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) t[u] = *(b + u < k1 ? p + (b + u) * stride : zero);
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc += t[u];
-  }
-  return acc;
-}
-
 template <int U = 8, class F>
 __device__ __forceinline__ double range_sum(int k0, int k1, F f) {
   double acc = 0.0;
@@ -123,8 +108,6 @@ __device__ __forceinline__ void lds_add(double* p, double v) {
   typedef __attribute__((address_space(3))) double* LPtr;
   __hip_atomic_fetch_add((LPtr)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
-
-__device__ __forceinline__ int div_k(int t, int K, unsigned km) { return K == 1 ? t : (int)__umulhi((unsigned)t, km); }
 
 __device__ __forceinline__ void tile_ij(int t, int& I, int& J) {
   I = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);

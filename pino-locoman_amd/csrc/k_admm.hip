@@ -35,8 +35,8 @@
 // The symmetric mat-vec uses the packed lower 4x4 tiles: each tile gives 4 row
 // partials (accumulated per lane over the lane's run of tiles in a tile row) and, off the
 // diagonal, 4 column partials; both go straight into a per-wave LDS accumulator with
-// ds_add_f64 (PL_ADMM_ATOMIC, r02e; the segment / column-partial arrays of r01 remain as
-// the #else branch).  The backward step's A x~ and A^T (rho z - y) are chunked CSR / CSC
+// ds_add_f64 (since r02e; r01 stored segment and column-partial arrays and summed them by
+// chunk, a path removed from the tree).  The backward step's A x~ and A^T (rho z - y) are chunked CSR / CSC
 // gathers (entry-order scatters into LDS row / column sums were measured slower in r04 and
 // removed).  The lanes of one ds_add instruction and the instructions
 // of one wave apply in a fixed order, so results are bit-identical for a problem
@@ -73,7 +73,10 @@ struct LateC {  // backward columns of node i
 struct AdmmLds {
   int prog_dbl;  // all ADMM programs (u16), rounded to 16 bytes, in doubles
   int per_wave;
-  int v, y, xn, r1, tcpl, trow, red, colp, zero, asb, asb_cap;
+  // pad0: where the removed r01 path kept its column partials' offset.  The struct is a kernel
+  // argument: dropping the word moves every later scalar load, so it leaves together with the
+  // `zero` slot, in a change that may re-measure.
+  int v, y, xn, r1, tcpl, trow, red, pad0, zero, asb, asb_cap;
 };
 
 }  // namespace
@@ -133,11 +136,12 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
   double* r1 = W + lm.r1;      // rhs_1 (dx part) completed by T0, read by the next forward 1
   double* tcpl = W + lm.tcpl;  // coupling-row products (before the mat-vec; aliases `red`)
   double* trow = W + lm.trow;  // rho z - y of the node's rows (after the mat-vec; aliases `red`)
-  double* seg = W + lm.red;    // mat-vec row segments [(lane + I) * 4 + r]
-  double* colp = W + lm.colp;  // mat-vec column partials, off-diagonal tiles in column-major order
+  double* acc5 = W + lm.red;   // mat-vec accumulator: output 4 I + r at acc5[5 I + r] (aliases `red`)
   double* part = W + lm.red;   // chunk sums of the row / column gathers (after the mat-vec)
   double* asb = W + lm.asb;    // A values of the backward node
-  double* zslot = W + lm.zero; // a 0.0 read by the clamped reductions
+  // a 0.0 only the removed r01 reductions read: the slot and its store stay until a change
+  // that may re-measure, since dropping them moves the LDS offsets and the device code
+  double* zslot = W + lm.zero;
   if (lane == 0) *zslot = 0.0;
 
   const double* __restrict__ As = d.As + (size_t)b * nnz;
@@ -279,45 +283,33 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
     const int K = an[i].nunit, T = an[i].ntile, ntl = an[i].ntl, nw = an[i].nw;
     const int Kn = an[next].nunit;
     const double2* pn = reinterpret_cast<const double2*>(Sg + an[next].s_off);
-    const unsigned km = an[i].kmagic;
     const double2* v2 = reinterpret_cast<const double2*>(v);
     int curI = -1;
     double sa[4] = {0.0, 0.0, 0.0, 0.0};
     bool use_tt = false;
-#if PL_ADMM_ATOMIC
     // accumulate y in LDS with ds_add_f64 (no return, no dependent round trips):
     // output 4 I + r lives at acc5[5 I + r] (a stride of 5 doubles spreads the banks)
-    double* acc5 = seg;
     for (int o = lane; o < 5 * T; o += 64) acc5[o] = 0.0;
     wsync();
     auto emit_row = [&](int I0) __attribute__((always_inline)) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) lds_add(acc5 + I0 * 5 + r, sa[r]);
     };
-#else
-    auto emit_row = [&](int I0) __attribute__((always_inline)) {
-      double2* sp = reinterpret_cast<double2*>(seg + (lane + I0) * 4);
-      sp[0] = make_double2(sa[0], sa[1]);
-      sp[1] = make_double2(sa[2], sa[3]);
-    };
-#endif
     auto pass = [&](int kb, bool last_pass) __attribute__((always_inline)) {
 #pragma unroll
       for (int k = 0; k < KM; ++k) {
         const int kk = kb + k;
         const int t = K * lane + kk;
-        int I, J, cidx;
+        int I, J;
         bool valid;
         if (use_tt) {  // precomputed (uniform choice)
           const uint32_t w = k == 0 ? tt.x : (k == 1 ? tt.y : (k == 2 ? tt.z : tt.w));
           I = (int)(w >> 24);
           J = (int)((w >> 16) & 0xff);
-          cidx = (int)(w & 0xffff);
           valid = I != 0xff;
         } else {
           valid = kk < K && t < ntl;
           tile_ij(t, I, J);
-          cidx = (J * (2 * T - J - 1)) / 2 + I - J - 1;
         }
         if (valid) {
           const double2 a0 = v2[2 * J], a1 = v2[2 * J + 1];
@@ -337,17 +329,8 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
               cp[2] += R.s[k][2 * r + 1].x * vi[r];
               cp[3] += R.s[k][2 * r + 1].y * vi[r];
             }
-#if PL_ADMM_ATOMIC
-            (void)cidx;
 #pragma unroll
             for (int c = 0; c < 4; ++c) lds_add(acc5 + J * 5 + c, cp[c]);
-#else
-            // column-major packed off-diagonal index: the partials of one output tile
-            // column are contiguous
-            double2* cpp = reinterpret_cast<double2*>(colp + cidx * 4);
-            cpp[0] = make_double2(cp[0], cp[1]);
-            cpp[1] = make_double2(cp[2], cp[3]);
-#endif
           }
           if (I != curI) {
             if (curI >= 0) emit_row(curI);
@@ -379,28 +362,11 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
     }
     if (curI >= 0) emit_row(curI);
     wsync();
-#if PL_ADMM_ATOMIC
-    (void)km;
 #pragma unroll
     for (int mm = 0; mm < MV; ++mm) {
       const int o = lane + 64 * mm;
       if (o < nw) y[o] = acc5[(o >> 2) * 5 + (o & 3)];
     }
-#else
-#pragma unroll
-    for (int mm = 0; mm < MV; ++mm) {
-      const int o = lane + 64 * mm;
-      if (o < nw) {
-        const int I = o >> 2, r = o & 3;
-        const int t0 = I * (I + 1) / 2;
-        const int lf = div_k(t0, K, km), ll = div_k(t0 + I, K, km);
-        const double rs = lds_sum(seg + I * 4 + r, lf, ll + 1, 4, zslot);
-        const int cb = (I * (2 * T - I - 1)) / 2;
-        const double cs = lds_sum(colp + r, cb, cb + T - 1 - I, 4, zslot);
-        y[o] = rs + cs;
-      }
-    }
-#endif
     wsync();
   };
 
@@ -638,11 +604,9 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
           const uint8_t* rowc = reinterpret_cast<const uint8_t*>(P + an[i].rowc);
           const uint32_t* rch = reinterpret_cast<const uint32_t*>(P + an[i].rch);
           const int rchn = an[i].rchn;
-#if PL_ADMM_ATOMIC
           const uint8_t* rchr = reinterpret_cast<const uint8_t*>(P + an[i].rchr);
           for (int o = lane; o < an[i].nrow; o += 64) part[o] = 0.0;  // row sums, by LDS f64 adds
           wsync();
-#endif
           for (int c0 = 0; c0 < rchn; c0 += 128) {  // two rounds of chunks per batch
             double acc[2];
 #pragma unroll
@@ -662,11 +626,7 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
               const int ch = c0 + lane + 64 * u;
-#if PL_ADMM_ATOMIC
               if (ch < rchn) lds_add(part + rchr[ch], acc[u]);
-#else
-              if (ch < rchn) part[ch] = acc[u];
-#endif
             }
           }
         }
@@ -674,18 +634,12 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
         T(5);
         // ---- update_z, update_y (relaxed)
         {
-          const int nrow = an[i].nrow, ro = an[i].row_off, rcp = an[i].rchptr;
+          const int nrow = an[i].nrow, ro = an[i].row_off;
 #pragma unroll
           for (int mm = 0; mm < MR; ++mm) {
             const int r = lane + 64 * mm;
             if (r < nrow) {
-#if PL_ADMM_ATOMIC
-              (void)rcp;
               const double zt = part[r];
-#else
-              const int k0 = P[rcp + r], k1 = P[rcp + r + 1];
-              const double zt = lds_sum<4>(part, k0, k1, 1, zslot);
-#endif
               double rr, ri;  // rho of the row and 1 / rho
               if constexpr (kRule) {  // k_qp_finish's rule on the stored l, u (same comparisons, same values)
                 const bool unb = LR.l[mm] < -PL_OSQP_INFTY * PL_MIN_SCALING && LR.u[mm] > PL_OSQP_INFTY * PL_MIN_SCALING;
@@ -715,12 +669,10 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
           const uint8_t* colr = reinterpret_cast<const uint8_t*>(P + an[i].colr);
           const uint32_t* cch = reinterpret_cast<const uint32_t*>(P + an[i].cch);
           const int cchn = an[i].cchn;
-#if PL_ADMM_ATOMIC
           // column sums by LDS f64 adds (the z update's reads of `part` are ahead in LDS order)
           const uint8_t* cchc = reinterpret_cast<const uint8_t*>(P + an[i].cchc);
           for (int o = lane; o < an[i].ncol; o += 64) part[o] = 0.0;
           wsync();
-#endif
           for (int c0 = 0; c0 < cchn; c0 += 128) {  // two rounds of chunks per batch
             double acc[2];
 #pragma unroll
@@ -740,11 +692,7 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
               const int ch = c0 + lane + 64 * u;
-#if PL_ADMM_ATOMIC
               if (ch < cchn) lds_add(part + cchc[ch], acc[u]);
-#else
-              if (ch < cchn) part[ch] = acc[u];
-#endif
             }
           }
         }
@@ -753,7 +701,6 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
       T(7);
       // ---- update_x and the next rhs = sigma x - q + A^T (rho z - y) (stores deferred)
       {
-        const int ccp0 = an[i].cchptr;
 #pragma unroll
         for (int mm = 0; mm < MV; ++mm) {
           const int c = lane + 64 * mm;
@@ -762,20 +709,9 @@ __global__ __launch_bounds__(64 * PPW, 1) void k_admm(PlDev d, int B, int N, int
             set2(pxa, mm, xnew);
             set2(pdx, mm, xnew - LC.x[mm]);
             double acc = sigma * xnew - LC.q[mm];
-#if PL_ADMM_ATOMIC
-            (void)ccp0;
             acc += part[c];
-#else
-            const int k0 = P[ccp0 + c], k1 = P[ccp0 + c + 1];
-            acc += lds_sum<4>(part, k0, k1, 1, zslot);
-#endif
             if (c < ndx) {  // rows of node i on dx_{i+1} complete rhs_{i+1}
-#if PL_ADMM_ATOMIC
               const double a2 = part[nw + c];
-#else
-              const int f0 = P[ccp0 + nw + c], f1 = P[ccp0 + nw + c + 1];
-              const double a2 = lds_sum<4>(part, f0, f1, 1, zslot);
-#endif
               prn = rkeep + a2;
               if (i == 0) r1[c] = prn;
             }
@@ -910,18 +846,11 @@ AdmmCfg admm_config(const PlOcpHandle* h) {
   o += 2;
   lm.r1 = o;
   o += up2(h->ndx);
-  // `red` is time-shared: coupling products (gathers) | mat-vec segments and column
-  // partials (mat-vec) | chunk sums and rho z - y (row / column gathers)
+  // `red` is time-shared: coupling products (gathers) | the mat-vec accumulator acc5
+  // (mat-vec) | chunk sums and rho z - y (row / column gathers)
   lm.red = o;
   lm.tcpl = o;
-#if PL_ADMM_ATOMIC
-  const int matv = 5 * T;  // the mat-vec accumulator acc5 (no segments, no column partials)
-  lm.colp = o;
-#else
-  const int segn = (64 + T) * 4;
-  const int matv = segn + T * (T - 1) / 2 * 4;
-  lm.colp = o + segn;
-#endif
+  const int matv = 5 * T;
   // `part` holds the chunk sums (chunked gathers) or the row / column sums (scatters)
   const int partn = up2(std::max(h->chunk_max, std::max(h->nrow_max, h->ncol_max)));
   lm.trow = o + partn;

@@ -7,6 +7,7 @@
 // uses one single-wave workgroup per (problem, node, 64-column chunk) and one
 // thread per local column, each thread seeding the tangent of its column and
 // writing the column's entries of the fixed sparsity pattern (CSC order inside the node).
+#include "dispatch.h"
 #include "dyn.h"
 #include "eval_common.h"
 #include "timeline.h"
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(64) void k_eval_values(PlDev d, int B, int N, int n
 }
 
 // Constraint Jacobian values on the fixed pattern.  One lane = one (node, local column)
-// of the work list d.jlist (api.hip build_jac_list): the columns that run the tree pass
+// of the work list d.jlist (api_build.hip build_jac_list): the columns that run the tree pass
 // are packed 64 per wave across node boundaries, the cheap ones follow; grid (waves, B).
 // Each lane seeds the tangent of its column and writes the column's entries (CSC order
 // inside the node).  Single-wave blocks retire independently.
@@ -236,18 +237,6 @@ __global__ __launch_bounds__(256) void k_hess(PlDev d, int N, int n, int np) {
     P[j] = h;
   }
 }
-
-#define PL_DISPATCH_DYN(dyn, KERNEL, ...)                                          \
-  switch (dyn) {                                                                    \
-    case PL_DYN_RNEA: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEA>, __VA_ARGS__); break; \
-    case PL_DYN_ACC: hipLaunchKernelGGL(KERNEL<PL_DYN_ACC>, __VA_ARGS__); break;   \
-    case PL_DYN_CV: hipLaunchKernelGGL(KERNEL<PL_DYN_CV>, __VA_ARGS__); break;     \
-    case PL_DYN_CA: hipLaunchKernelGGL(KERNEL<PL_DYN_CA>, __VA_ARGS__); break;     \
-    case PL_DYN_ACCNB: hipLaunchKernelGGL(KERNEL<PL_DYN_ACCNB>, __VA_ARGS__); break; \
-    case PL_DYN_CVNB: hipLaunchKernelGGL(KERNEL<PL_DYN_CVNB>, __VA_ARGS__); break;   \
-    case PL_DYN_RNEAFD: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEAFD>, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<PL_DYN_ABA>, __VA_ARGS__); break;           \
-  }
 
 void launch_eval_values(PlOcpHandle* h, const double* xsrc) {
   const int total = h->B * h->N;

@@ -550,7 +550,7 @@ __global__ __launch_bounds__(NT) void k_fchain(PlDev d, int N, int m, int nnz, i
     CU32 pcl = cp + 3 * X + 1;
     const int npc = fn->npc;
     CU32 cwl = pcl + npc;
-    // general coupling program (api.hip build_factor_prog): crow[nc] | cwptr[nc + 1] | pcl[npc] |
+    // general coupling program (api_build.hip build_factor_prog): crow[nc] | cwptr[nc + 1] | pcl[npc] |
     // cw[ncw] | xcptr[X + 1] | xc[nxc]
     const int nc = gc ? fn->nc : 0;
     CU32 gcwptr = cp + nc;

@@ -5,11 +5,12 @@
 //     H_L = diag(objective Hessian) + sum_i H_i,   H_i = sum_{rows r of node i} lam_r d^2 g_r / dw_i^2
 // is block diagonal over the w_i: the same sparsity as the factor's diagonal blocks Kt_ii.
 //
-// The work list d.hlist holds the (node i, column pair j <= k of w_i) pairs (api.hip
-// build_hess_list; pairs with an rnea tau_j column are structurally zero and not listed).  A
+// The work list d.hlist holds the (node i, column pair j <= k of w_i) pairs (api_ip.hip
+// pl_ocp_set_solver; pairs with an rnea tau_j column are structurally zero and not listed).  A
 // pair's node rows are evaluated in hyper-dual numbers seeded on columns j and k (ad.h HDual)
 // and the e1 e2 parts contracted with lam: H_i[k][j] = sum_r lam_r g_r.c, written packed lower
 // (k (k + 1) / 2 + j from the node's offset d.hoff[i]), the layout k_fnode assembles Kt_ii in.
+#include "dispatch.h"
 #include "dyn.h"
 #include "eval_common.h"
 #include "hess_tree.h"
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(64) void k_lag_hess_pb(PlDev d, int B, int N, int n
   HDual kst[PL_KIN_STORE];
   const int2 w = d.hlist[blockIdx.x];
   const int wx = __builtin_amdgcn_readfirstlane(w.x);
-  const int i = wx & 0xffff, only_ch = (wx >> 16) - 1;  // the pair's chain (api.hip set_solver)
+  const int i = wx & 0xffff, only_ch = (wx >> 16) - 1;  // the pair's chain (api_ip.hip pl_ocp_set_solver)
   const int jk = __builtin_amdgcn_readfirstlane(w.y);
   const int j = jk & 0xffff, k = jk >> 16;
   const PlNode nd = d.nodes[i];
@@ -239,8 +240,8 @@ __global__ __launch_bounds__(64) void k_lag_hess_tree(PlDev d, int B, int n, int
 }
 
 // r06: the (dq, dq) and (dq, dv) pairs by forward-over-reverse columns (hess_tree.h tree_col): one work
-// item per (node, chain, dq column j) with the mask of its pairs' other coordinates (api.hip
-// set_solver groups d.htr that way: every pair is written by the item of its smaller index j), one item
+// item per (node, chain, dq column j) with the mask of its pairs' other coordinates (api_ip.hip
+// pl_ocp_set_solver groups d.htr that way: every pair is written by the item of its smaller index j), one item
 // per wave, one problem per lane.  PL_PATH_HESS_PAIRS keeps k_lag_hess_tree<false> per pair.
 template <bool WHOLE>
 __global__ __launch_bounds__(64) void k_lag_hess_col(PlDev d, int B, int n, int m, int np, long long hl_stride,
@@ -363,17 +364,6 @@ __global__ __launch_bounds__(64) void k_lag_hess_cone(PlDev d, int B, int m, int
   d.Hlag[(size_t)b * hl_stride + d.hoff[i] + col * (col + 1) / 2 + col] = lam * h;
 }
 
-#define PL_DISPATCH_DYN(dyn, KERNEL, ...)                                            \
-  switch (dyn) {                                                                      \
-    case PL_DYN_RNEA: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEA>, __VA_ARGS__); break;   \
-    case PL_DYN_ACC: hipLaunchKernelGGL(KERNEL<PL_DYN_ACC>, __VA_ARGS__); break;     \
-    case PL_DYN_CV: hipLaunchKernelGGL(KERNEL<PL_DYN_CV>, __VA_ARGS__); break;       \
-    case PL_DYN_CA: hipLaunchKernelGGL(KERNEL<PL_DYN_CA>, __VA_ARGS__); break;       \
-    case PL_DYN_ACCNB: hipLaunchKernelGGL(KERNEL<PL_DYN_ACCNB>, __VA_ARGS__); break; \
-    case PL_DYN_CVNB: hipLaunchKernelGGL(KERNEL<PL_DYN_CVNB>, __VA_ARGS__); break;   \
-    default: hipLaunchKernelGGL(KERNEL<PL_DYN_ABA>, __VA_ARGS__); break;             \
-  }
-
 // The active problems of this interior-point iteration in ascending order (one 256-thread
 // block; a ballot prefix per wave, wave offsets in LDS): the Hessian kernels map lanes to
 // d.ip_act, so the waves past the active count exit at once when most problems have
@@ -438,7 +428,7 @@ void launch_lag_hess(PlOcpHandle* h) {
     hipLaunchKernelGGL(k_lag_hess_cone, dim3((h->hcone_len + 63) / 64, h->B), dim3(64), 0, h->stream, h->d, h->B, h->m,
                        h->np, h->hl_stride, h->hcone_len);
   if (h->hl_len > 0)
-    PL_DISPATCH_DYN(h->oc.dyn, k_lag_hess_pb, dim3(h->hl_len, (h->B + 63) / 64), dim3(64), 0, h->stream, h->d, h->B, h->N,
+    PL_DISPATCH_DYN_IP(h->oc.dyn, k_lag_hess_pb, dim3(h->hl_len, (h->B + 63) / 64), dim3(64), 0, h->stream, h->d, h->B, h->N,
                   h->n, h->m, h->np, h->hl_stride);
   if (prof) {
     hipEventRecord(h->prof_hev[h->prof_hn][1], h->stream);

@@ -20,6 +20,7 @@
 // every kernel that checks info->done / ipinfo->active.
 #include <math.h>
 
+#include "dispatch.h"
 #include "eval_common.h"
 #include "pinoloco.h"  // PL_PATH_* (pl_ocp_desc.debug_paths)
 
@@ -819,17 +820,6 @@ __global__ void k_ip_finish(PlDev d, int B) {
   info->f = ip->f;
 }
 
-#define PL_DISPATCH_DYN(dyn, KERNEL, ...)                                          \
-  switch (dyn) {                                                                    \
-    case PL_DYN_RNEA: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEA>, __VA_ARGS__); break; \
-    case PL_DYN_ACC: hipLaunchKernelGGL(KERNEL<PL_DYN_ACC>, __VA_ARGS__); break;   \
-    case PL_DYN_CV: hipLaunchKernelGGL(KERNEL<PL_DYN_CV>, __VA_ARGS__); break;     \
-    case PL_DYN_CA: hipLaunchKernelGGL(KERNEL<PL_DYN_CA>, __VA_ARGS__); break;     \
-    case PL_DYN_ACCNB: hipLaunchKernelGGL(KERNEL<PL_DYN_ACCNB>, __VA_ARGS__); break; \
-    case PL_DYN_CVNB: hipLaunchKernelGGL(KERNEL<PL_DYN_CVNB>, __VA_ARGS__); break;   \
-    default: hipLaunchKernelGGL(KERNEL<PL_DYN_ABA>, __VA_ARGS__); break;           \
-  }
-
 #define PL_IP_INERTIA_CAP 8  // shifts per Newton system (1e-4 x 100^7 = 1e10 from a clean start)
 
 // Factor the Newton system, with the inertia correction when the Lagrangian Hessian is in
@@ -888,7 +878,7 @@ void enqueue_ip(PlOcpHandle* h) {
       launch_admm_init_zero(h);  // k_ip_refine zeroed x, z, y
       launch_admm(h, 1, 0, 0);
     }
-    PL_DISPATCH_DYN(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st,
+    PL_DISPATCH_DYN_IP(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st,
                     0);
   }
   h->set = saved;
@@ -919,7 +909,7 @@ void enqueue_ip_direction(PlOcpHandle* h) {
     launch_admm_init_zero(h);
     launch_admm(h, 1, 0, 0);
   }
-  PL_DISPATCH_DYN(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st, 1);
+  PL_DISPATCH_DYN_IP(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st, 1);
   h->set = saved;
 }
 
@@ -945,7 +935,7 @@ int enqueue_ip_stage(PlOcpHandle* h, int stage, int arg) {
     case PL_IP_STAGE_STEP:
       launch_eval_values(h, h->d.x);
       launch_objective(h);
-      PL_DISPATCH_DYN(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st,
+      PL_DISPATCH_DYN_IP(h->oc.dyn, k_ip_step, dim3(h->B), dim3(256), 0, h->stream, h->d, h->N, h->n, h->m, h->np, st,
                       0);
       return 0;
   }

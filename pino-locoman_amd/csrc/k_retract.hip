@@ -8,6 +8,7 @@
 // k_dyn / k_mpc_finish, so the tree passes of retract_node (retract.h) keep their per-thread
 // arrays; every problem reads its own parameters (x_init, step sizes).  A thread's result
 // depends on its problem's x and p and on its node only, not on the batch or the row count.
+#include "dispatch.h"
 #include "retract.h"
 #include "state.h"
 
@@ -25,18 +26,6 @@ __global__ __launch_bounds__(64) void k_retract(PlDev d, int B, int R, int N, in
   const pl::RetractOut o{row[0], row[1], row[2], row[3], row[4], row[5], 1};
   pl::retract_node(*d.model, O, DYN, d.nodes, N, p, d.x + (size_t)b * n, p + O.P.x_init, i, o);
 }
-
-#define PL_DISPATCH_DYN(dyn, KERNEL, ...)                                          \
-  switch (dyn) {                                                                    \
-    case PL_DYN_RNEA: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEA>, __VA_ARGS__); break; \
-    case PL_DYN_ACC: hipLaunchKernelGGL(KERNEL<PL_DYN_ACC>, __VA_ARGS__); break;   \
-    case PL_DYN_CV: hipLaunchKernelGGL(KERNEL<PL_DYN_CV>, __VA_ARGS__); break;     \
-    case PL_DYN_CA: hipLaunchKernelGGL(KERNEL<PL_DYN_CA>, __VA_ARGS__); break;     \
-    case PL_DYN_ACCNB: hipLaunchKernelGGL(KERNEL<PL_DYN_ACCNB>, __VA_ARGS__); break; \
-    case PL_DYN_CVNB: hipLaunchKernelGGL(KERNEL<PL_DYN_CVNB>, __VA_ARGS__); break;   \
-    case PL_DYN_RNEAFD: hipLaunchKernelGGL(KERNEL<PL_DYN_RNEAFD>, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<PL_DYN_ABA>, __VA_ARGS__); break;           \
-  }
 
 // steps in [1, N]; terminal (0 / 1) needs steps == N (the callers check); out: L.total doubles
 void launch_retract(PlOcpHandle* h, int steps, int terminal, double* out) {

@@ -61,14 +61,11 @@ struct PlNode {
 // elements are 8 double2 (row r, cols 2h, 2h + 1 -> pair j = 2 r + h) stored at
 // s_off + ((k * 8 + j) * 64 + l) * 2, so each 16-byte load of a wave is 1 KiB contiguous.
 #define PL_CHUNK 6
-// ADMM sweep kernel limits (one wave per problem, k_admm.hip)
-#ifndef PL_ADMM_ATOMIC
 #ifndef PL_IP_HESS_EXACT  // include/pinoloco.h (pl_ip_settings.hessian)
 #define PL_IP_HESS_EXACT 0
 #define PL_IP_HESS_GN 1
 #endif
-#define PL_ADMM_ATOMIC 1  // k_admm mat-vec: accumulate y with LDS f64 atomics (0: segment sums)
-#endif
+// ADMM sweep kernel limits (one wave per problem, k_admm.hip)
 #define PL_ADMM_KM 4        // factor tile slots per lane held in registers (more: extra passes)
 #define PL_ADMM_CWM 2       // w entries per coupling row held in registers (more: LDS path)
 #define PL_ADMM_XCM 1       // coupling entries per dx_{i+1} column held in registers
@@ -91,7 +88,8 @@ struct PlNode {
 #define PL_RHO_EQ_OVER_INEQ 1e3
 struct PlAdmmNode {
   int nw, nrow, ncol, ncpl, nent, nunit, ntile, ntl;  // nunit = K slots, ntile = T, ntl = tiles
-  unsigned kmagic;  // ceil(2^32 / K): t / K == umulhi(t, kmagic) for the tile counts used
+  unsigned kmagic;  // ceil(2^32 / K): t / K == umulhi(t, kmagic) for the tile counts used.  Only the
+                    // removed r01 mat-vec read it; dropping it shifts every load of the table
   int x_off, row_off, ent_off, s_off;
   int prog, prog_len;
   int rowe, rowc, colr, cwptr, cwp, cxptr, cxp, ccptr, ccp, xcptr, xcp;
@@ -381,7 +379,7 @@ struct PlOcpHandle {
   int* h_nodes_raw;
   // optional per-kernel timing of the ADMM launches (HIP events on the handle's stream)
   int profile;
-  // outside the MPC-graph key (api.hip kMpcKeyBytes): set by the first Jacobian evaluation,
+  // outside the MPC-graph key (api_mpc.hip kMpcKeyBytes): set by the first Jacobian evaluation,
   // which runs eagerly; a debug write of Araw clears it and the key
   int jac_cheap_ok;                 // the cheap columns' constant entries are in d.Araw
   // also outside the key: who wrote d.rho last, set while the writer is enqueued (the same

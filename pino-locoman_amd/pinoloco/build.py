@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 LIB = os.path.join(HERE, "libpinoloco.so")
-SOURCES = ["api.hip", "api_build.hip", "api_casadi.hip", "k_eval.hip", "k_qp.hip", "k_admm.hip", "k_factor.hip", "k_dyn.hip", "k_admm2.hip", "k_ip.hip", "k_admm_rc.hip", "k_hess.hip", "k_retract.hip", "k_plant.hip",
+SOURCES = ["api.hip", "api_ip.hip", "api_mpc.hip", "api_debug.hip", "api_build.hip", "api_casadi.hip", "k_eval.hip", "k_qp.hip", "k_admm.hip", "k_factor.hip", "k_dyn.hip", "k_admm2.hip", "k_ip.hip", "k_admm_rc.hip", "k_hess.hip", "k_retract.hip", "k_plant.hip",
            "k_record.hip", "k_dyn_jac.hip", "k_rho.hip"]
 ARCH = os.environ.get("PL_OFFLOAD_ARCH", "gfx950")
 
@@ -101,7 +101,15 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-4000:]}")
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    # compilers at once: MAX_JOBS when set and positive, else at most 16 (a shared machine
+    # reports many more CPUs than one command may use)
+    try:
+        jobs = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        jobs = 0
+    if jobs <= 0:
+        jobs = min(16, os.cpu_count() or 1)
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), jobs)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     tmp = LIB + ".tmp"
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", tmp] + objs

@@ -1,4 +1,4 @@
-"""MPC-step graph replay (pl_mpc_step, api.hip): the OSQP-SQP launches of a step are
+"""MPC-step graph replay (pl_mpc_step, api_mpc.hip): the OSQP-SQP launches of a step are
 captured once into a HIP graph and replayed.  A replay must be the eager launch sequence:
 states, iterates and solver statistics bit-identical to a handle created with
 the no_mpc_graph debug path, including across a setter that changes the handle mid-loop (re-capture), and the capture /
