@@ -277,7 +277,8 @@ int pl_mpc_get_plant(const pl_ocp* o, int* mode, int* substeps);
  * v[0:6] of the free-flyer, linear then angular, in the base frame (the base rows of
  * pinocchio::aba's tau); read by PL_PLANT_ABA only.  state_noise [batch][ndx] or NULL (= none):
  * the MPC plans from the measured state x_init = state_integrate(x_state, noise)
- * (run_mpc.py:79-82) while x_state stays the true state; under either plant. */
+ * (run_mpc.py:79-82) while x_state stays the true state; under either plant.  Either argument is
+ * refused while pl_mpc_set_noise (below) draws that quantity afresh at every step. */
 int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, const double* state_noise);
 /* Ground contact at the feet and a joint PD loop, options of PL_PLANT_ABA (not a mode of their
  * own).  With them the ground pushes back at the feet instead of the commanded forces, and the
@@ -501,6 +502,56 @@ int pl_mpc_timeline_state(pl_ocp* o, int* seg /*[batch]*/, int* gait_type /*[bat
  * Validates the keyframes as pl_mpc_set_timeline does.  Works on a handle without a device. */
 int pl_mpc_timeline_host(const pl_ocp* o, int k, double t0, const pl_mpc_keyframe* keys, int count, double* p,
                          double* x, int* seg);
+
+/* Per-step random state noise and base wrench, drawn on the device: the fresh Gaussian draw on
+ * x_init at every MPC step that run_mpc.py:79-82 sketches, and per-step process noise on the base
+ * wrench.  Off by default, and then the gait / warm-start launch does exactly what it does without
+ * it.  The generator is counter-based, Philox4x32-10 (Salmon et al., SC'11): a draw is a pure
+ * function of (the problem's seed, the stream, the step k, the component).  It does not depend on
+ * the batch size, the problem's slot, the launch geometry, the steps that ran before or the GPU
+ * that holds the shard; a rollout restarted at step k continues the same sequence.
+ *   block address  counter (k, i, stream, 0), key (seed & 0xffffffff, seed >> 32); i the block
+ *                  inside the stream; stream 0 the state noise, 1 the base wrench
+ *   uniforms       of the block's words w0..w3, U(a, b) = ((a >> 5) 2^26 + (b >> 6)) 2^-53 (exact, in
+ *                  [0, 1)):  u1 = 1 - U(w0, w1),  theta = 0x1.921fb54442d18p+2 U(w2, w3)
+ *   normals        r = sqrt(-2 log u1), z_{2i} = r cos theta, z_{2i+1} = r sin theta; component j of
+ *                  a stream is normal j & 1 of block j >> 1
+ *   state noise    noise_j = state_sigma[b][j] z_j, j < ndx: the MPC of step k plans from
+ *                  x_init = state_integrate(x_state, noise) while x_state stays the true state
+ *   base wrench    w_c = det_c + wrench_sigma[b][c] z_c, c < 6, product and sum each rounded; det is
+ *                  the push window's wrench of step k (pl_mpc_set_push), zero without a schedule;
+ *                  read by PL_PLANT_ABA only, as every base wrench
+ * The gait / warm-start launch of step k draws them, outside the captured step: switching a stream
+ * on or off and new seeds or sigmas never re-capture.  Both solvers and both plants work alike.
+ * seed [batch]; state_sigma [batch][ndx] or NULL (that stream off); wrench_sigma [batch][6] or NULL
+ * (that stream off).  seed == NULL switches both off and zeroes the base wrench unless a push
+ * schedule owns it.  Refused before any device work, with the problem and the component in
+ * pl_last_error: a negative or non-finite sigma; seeds without either sigma array.  One owner per
+ * buffer: state_sigma is refused while a state_noise of pl_mpc_set_disturbance is set, wrench_sigma
+ * while a base_wrench of it is (clear that one first); while a stream is set,
+ * pl_mpc_set_disturbance with the matching argument is refused.  A push schedule and the random
+ * wrench combine.  Last refusal: a handle without a device.  The settings persist across
+ * pl_mpc_setup; there is no generator state to clear. */
+int pl_mpc_set_noise(pl_ocp* o, const unsigned long long* seed, const double* state_sigma, const double* wrench_sigma);
+int pl_mpc_get_noise(const pl_ocp* o, int* state_on, int* wrench_on);   /* either may be NULL */
+/* What the last gait / warm-start launch planned with: the state noise [batch][ndx] and the base
+ * wrench [batch][6] in the handle's device buffers (the drawn values while a stream is on, else
+ * what pl_mpc_set_disturbance / pl_mpc_set_push left there), read through the pinned staging
+ * buffer.  Either pointer may be NULL. */
+int pl_mpc_noise_state(pl_ocp* o, double* state_noise, double* base_wrench);
+/* One problem's draw of step k >= 0 and its x_init on the host, the code the kernel runs:
+ * state_sigma [ndx] or NULL (stream off: zero noise, x_init = x_state), wrench_sigma [6] or NULL
+ * (stream off: the wrench is det_wrench), det_wrench [6] or NULL (zero), x_state [nx] (NULL
+ * without x_init).  Outputs, each may be NULL: state_noise [ndx], base_wrench [6], x_init [nx].
+ * Validates the sigmas as pl_mpc_set_noise does.  Works on a handle without a device. */
+int pl_mpc_noise_host(const pl_ocp* o, int k, unsigned long long seed, const double* state_sigma,
+                      const double* wrench_sigma, const double* det_wrench, const double* x_state,
+                      double* state_noise, double* base_wrench, double* x_init);
+/* One Philox4x32-10 block on the host: 32-bit words ctr [4], key [2] -> out [4]. */
+int pl_rng_block_host(const unsigned* ctr, const unsigned* key, unsigned* out);
+/* The uniforms of one block's words [4] on the host: *u1 = 1 - U(w0, w1) in (0, 1], exact;
+ * *theta = 0x1.921fb54442d18p+2 U(w2, w3). */
+int pl_rng_uniforms_host(const unsigned* words, double* u1, double* theta);
 int pl_ocp_sync(pl_ocp* o);
 
 /* Host-side state maps, x = [q, v], dx = [dq, dv]
@@ -655,9 +706,14 @@ int pl_debug_consts(const pl_ocp* o, void* model_out, void* oc_out, int* sizes);
 int pl_debug_admm(pl_ocp* o, int niter, int reset);
 /* Ruiz scaling + scaled data alone on the raw arrays as they are (no evaluation, no factor). */
 int pl_debug_qp_setup(pl_ocp* o);
-/* The gait / warm-start launch of MPC step k alone (x_init, push window, timeline, schedule,
- * warm start), then a synchronise: p and x can be read before any solve overwrites the iterate. */
+/* The gait / warm-start launch of MPC step k alone (random draw, x_init, push window, timeline,
+ * schedule, warm start), then a synchronise: p and x can be read before any solve overwrites the iterate. */
 int pl_debug_mpc_prepare(pl_ocp* o, int k);
+/* The device's raw Philox blocks for the seeds given to pl_mpc_set_noise: block i < n_blocks of
+ * problem b has the counter (k, i0 + i, stream, c3) and the key of seed[b]; the loop's draws have
+ * i0 = c3 = 0.  out [batch][n_blocks][4] 32-bit words.  The integer part of the generator, to be
+ * compared bit for bit away from any libm. */
+int pl_debug_rng(pl_ocp* o, unsigned k, unsigned stream, unsigned i0, unsigned c3, int n_blocks, unsigned* out);
 /* One termination check on the current iterates and scaled data, then (unscale) the step
  * write-back; read status / pri_res / dua_res with pl_mpc_get_stats. */
 int pl_debug_check(pl_ocp* o, int final_check, int unscale);

@@ -23,8 +23,9 @@ void pl_set_error(const char* fmt, ...) {
 
 
 extern "C" const char* pl_last_error(void) { return g_err; }
-// 2: pl_mpc_set_timeline and its siblings, pl_debug_mpc_prepare
-extern "C" int pl_version(void) { return 2; }
+// 2: pl_mpc_set_timeline and its siblings, pl_debug_mpc_prepare; 3: pl_mpc_set_noise and its
+// siblings, pl_rng_*_host, pl_debug_rng
+extern "C" int pl_version(void) { return 3; }
 
 // Build provenance: build.py passes the sha256 of csrc/* + include/*.h (PL_SRC_SHA), so a
 // caller can tell which sources a pushed binary was built from (bench.py prints it,

@@ -301,3 +301,25 @@ extern "C" int pl_debug_check(pl_ocp* o, int final_check, int unscale) {
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+// Tests: the device's raw Philox blocks (noise.h, k_rng_blocks) for the seeds pl_mpc_set_noise
+// holds: block i of problem b at the counter (k, i0 + i, stream, c3); the loop's draws have
+// i0 = c3 = 0.  The integer part of the generator, away from any libm.
+extern "C" int pl_debug_rng(pl_ocp* o, unsigned k, unsigned stream, unsigned i0, unsigned c3, int n_blocks,
+                            unsigned* out) {
+  if (!o || !out) { pl_set_error("pl_debug_rng: null argument"); return -1; }
+  if (n_blocks < 1 || n_blocks > 65536) { pl_set_error("pl_debug_rng: n_blocks %d outside [1, 65536]", n_blocks); return -1; }
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  if (!h->rng_seed) { pl_set_error("pl_debug_rng: no seeds were given (pl_mpc_set_noise)"); return -1; }
+  const size_t words = (size_t)h->B * n_blocks * 4;
+  unsigned* dev = nullptr;
+  PL_CHECK_HIP(hipMalloc((void**)&dev, words * sizeof(unsigned)));
+  launch_rng_blocks(h, k, stream, i0, c3, n_blocks, dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dev, words * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(dev);
+  PL_CHECK_HIP(e);
+  return 0;
+}

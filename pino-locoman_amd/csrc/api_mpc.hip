@@ -2,6 +2,7 @@
 // contact, the step with its graph capture and replay, state / stats / export / download, the
 // rollout log with its metrics and push schedule, and the gait and command timelines.
 #include "api_internal.h"
+#include "noise.h"
 #include "plant.h"
 #include "record.h"
 #include "timeline.h"
@@ -53,12 +54,22 @@ extern "C" int pl_mpc_set_disturbance(pl_ocp* o, const double* base_wrench, cons
     pl_set_error("pl_mpc_set_disturbance: a push schedule is set (pl_mpc_set_push) and owns the base wrench");
     return -1;
   }
+  if (base_wrench && h->rng_wrench_on) {
+    pl_set_error("pl_mpc_set_disturbance: a random base wrench is set (pl_mpc_set_noise) and owns the base wrench");
+    return -1;
+  }
+  if (state_noise && h->rng_state_on) {  // one owner of d.plant_noise
+    pl_set_error("pl_mpc_set_disturbance: a random state noise is set (pl_mpc_set_noise) and owns the state noise");
+    return -1;
+  }
   const size_t wb = (size_t)h->B * 6 * 8, nb = (size_t)h->B * h->ndx * 8;
   if (base_wrench) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_w, base_wrench, wb, hipMemcpyHostToDevice, h->stream));
-  else if (!h->push_on) PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, wb, h->stream));  // k_plant always reads it: zero = none
+  else if (!h->push_on && !h->rng_wrench_on)  // k_plant always reads it: zero = none
+    PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, wb, h->stream));
   if (state_noise) PL_CHECK_HIP(hipMemcpyAsync(h->d.plant_noise, state_noise, nb, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->plant_noise_on = state_noise ? 1 : 0;  // off: k_mpc_prepare's plain copy of x_state
+  h->dist_wrench_on = base_wrench ? 1 : 0;
   return 0;
 }
 
@@ -494,6 +505,7 @@ extern "C" int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, 
   }
   REQUIRE_DEVICE(o);
   PlOcpHandle* h = &o->h;
+  h->dist_wrench_on = 0;  // set or cleared, the schedule overwrites what pl_mpc_set_disturbance left in d.plant_w
   if (off) {
     h->push_on = 0;
     PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, B * 6 * 8, h->stream));
@@ -506,6 +518,116 @@ extern "C" int pl_mpc_set_push(pl_ocp* o, const int* k_start, const int* k_end, 
   PL_CHECK_HIP(hipMemcpyAsync(h->push_w, wrench, B * 6 * 8, hipMemcpyHostToDevice, h->stream));
   PL_CHECK_HIP(hipStreamSynchronize(h->stream));
   h->push_on = 1;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Per-step random state noise and base wrench (noise.h): seeds and sigmas per problem in device
+// buffers that k_mpc_prepare alone reads.  Their state sits behind the MPC graph key (state.h),
+// like the push schedule's; the draws land in d.plant_noise / d.plant_w, which the handle owns.
+static int sigma_check(const char* who, size_t b, const char* name, const double* s, int width) {
+  for (int j = 0; s && j < width; ++j)
+    if (!std::isfinite(s[j]) || s[j] < 0.0) {
+      pl_set_error("%s: problem %zu: %s[%d] = %g is negative or not finite", who, b, name, j, s[j]);
+      return -1;
+    }
+  return 0;
+}
+
+extern "C" int pl_mpc_set_noise(pl_ocp* o, const unsigned long long* seed, const double* state_sigma,
+                                const double* wrench_sigma) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  PlOcpHandle* h = &o->h;
+  const size_t B = h->B, ndx = h->ndx;
+  if (seed) {
+    if (!state_sigma && !wrench_sigma) {
+      pl_set_error("pl_mpc_set_noise: seeds without state_sigma and without wrench_sigma (seed == NULL switches the noise off)");
+      return -1;
+    }
+    for (size_t b = 0; b < B; ++b)
+      if (sigma_check("pl_mpc_set_noise", b, "state_sigma", state_sigma ? state_sigma + b * ndx : nullptr, (int)ndx) ||
+          sigma_check("pl_mpc_set_noise", b, "wrench_sigma", wrench_sigma ? wrench_sigma + b * 6 : nullptr, 6))
+        return -1;
+    if (state_sigma && h->plant_noise_on) {  // one owner of d.plant_noise
+      pl_set_error("pl_mpc_set_noise: a state_noise of pl_mpc_set_disturbance is set and owns the state noise; clear it first");
+      return -1;
+    }
+    if (wrench_sigma && h->dist_wrench_on) {  // one owner of d.plant_w beside the push schedule
+      pl_set_error("pl_mpc_set_noise: a base_wrench of pl_mpc_set_disturbance is set and owns the base wrench; clear it first");
+      return -1;
+    }
+  }
+  REQUIRE_DEVICE(o);
+  const bool wrench_on = seed && wrench_sigma;
+  if (seed) {
+    if (!h->rng_seed && (dalloc(o, &h->rng_seed, B) || dalloc(o, &h->rng_sigma, B * ndx) || dalloc(o, &h->rng_wsigma, 6 * B)))
+      return -2;
+    // the stream orders the copies after an earlier prepare launch that still reads the old values
+    PL_CHECK_HIP(hipMemcpyAsync(h->rng_seed, seed, B * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+    if (state_sigma) PL_CHECK_HIP(hipMemcpyAsync(h->rng_sigma, state_sigma, B * ndx * 8, hipMemcpyHostToDevice, h->stream));
+    if (wrench_sigma) PL_CHECK_HIP(hipMemcpyAsync(h->rng_wsigma, wrench_sigma, B * 6 * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  // the random wrench gone (or everything off) and no schedule that rewrites it: zero = none
+  if (!wrench_on && !h->push_on && (!seed || h->rng_wrench_on)) {
+    PL_CHECK_HIP(hipMemsetAsync(h->d.plant_w, 0, B * 6 * 8, h->stream));
+    h->dist_wrench_on = 0;
+  }
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));  // the caller's arrays are read until the copies have run
+  h->rng_state_on = seed && state_sigma ? 1 : 0;
+  h->rng_wrench_on = wrench_on ? 1 : 0;
+  return 0;
+}
+
+extern "C" int pl_mpc_get_noise(const pl_ocp* o, int* state_on, int* wrench_on) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (state_on) *state_on = o->h.rng_state_on;
+  if (wrench_on) *wrench_on = o->h.rng_wrench_on;
+  return 0;
+}
+
+extern "C" int pl_mpc_noise_state(pl_ocp* o, double* state_noise, double* base_wrench) {
+  REQUIRE_DEVICE(o);
+  PlOcpHandle* h = &o->h;
+  const size_t nb = (size_t)h->B * h->ndx * 8, wb = (size_t)h->B * 6 * 8;
+  if (stage_reserve(o, nb + wb, "pl_mpc_noise_state")) return -2;
+  char* st = (char*)o->dl_host;
+  PL_CHECK_HIP(hipMemcpyAsync(st, h->d.plant_noise, nb, hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipMemcpyAsync(st + nb, h->d.plant_w, wb, hipMemcpyDeviceToHost, h->stream));
+  PL_CHECK_HIP(hipStreamSynchronize(h->stream));
+  if (state_noise) memcpy(state_noise, st, nb);
+  if (base_wrench) memcpy(base_wrench, st + nb, wb);
+  return 0;
+}
+
+extern "C" int pl_mpc_noise_host(const pl_ocp* o, int k, unsigned long long seed, const double* state_sigma,
+                                 const double* wrench_sigma, const double* det_wrench, const double* x_state,
+                                 double* state_noise, double* base_wrench, double* x_init) {
+  if (!o) { pl_set_error("null handle"); return -1; }
+  if (k < 0) { pl_set_error("pl_mpc_noise_host: step %d is negative", k); return -1; }
+  if (x_init && !x_state) { pl_set_error("pl_mpc_noise_host: x_init needs x_state"); return -1; }
+  const PlOcpHandle& h = o->h;
+  if (sigma_check("pl_mpc_noise_host", 0, "state_sigma", state_sigma, h.ndx) ||
+      sigma_check("pl_mpc_noise_host", 0, "wrench_sigma", wrench_sigma, 6))
+    return -1;
+  for (int c = 0; det_wrench && c < 6; ++c)
+    if (!std::isfinite(det_wrench[c])) {
+      pl_set_error("pl_mpc_noise_host: det_wrench[%d] = %g is not finite", c, det_wrench[c]);
+      return -1;
+    }
+  pl::noise_prepare_host(h.model, h.oc, h.nx, k, seed, state_sigma, wrench_sigma, det_wrench, x_state, state_noise,
+                         base_wrench, x_init);
+  return 0;
+}
+
+extern "C" int pl_rng_block_host(const unsigned* ctr, const unsigned* key, unsigned* out) {
+  if (!ctr || !key || !out) { pl_set_error("pl_rng_block_host: null argument"); return -1; }
+  pl::philox4x32_10(ctr, key, out);
+  return 0;
+}
+
+extern "C" int pl_rng_uniforms_host(const unsigned* words, double* u1, double* theta) {
+  if (!words || !u1 || !theta) { pl_set_error("pl_rng_uniforms_host: null argument"); return -1; }
+  pl::rng_uniforms(words, u1, theta);
   return 0;
 }
 

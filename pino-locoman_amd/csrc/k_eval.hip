@@ -10,6 +10,7 @@
 #include "dispatch.h"
 #include "dyn.h"
 #include "eval_common.h"
+#include "noise.h"
 #include "timeline.h"
 
 using pl::VecIn;
@@ -400,9 +401,11 @@ void launch_line_search(PlOcpHandle* h) {
 // MPC step k, before the solve: parameters (x_init, gait schedule at
 // t0 + k dt_min) and warm start (forces <- f_des masked by the new schedule;
 // ocp_whole_body_rnea.py:207-235).  k == 0 keeps the initial guess.
-// noise (pl_mpc_set_disturbance, null: none): the MPC plans from the measured state
-// x_init = state_integrate(x_state, noise_b), the "add noise to x_init" of run_mpc.py:79-82;
+// noise (pl_mpc_set_disturbance or the draw below, null: none): the MPC plans from the measured
+// state x_init = state_integrate(x_state, noise_b), the "add noise to x_init" of run_mpc.py:79-82;
 // x_state stays the true state.
+// rng_seed [B], rng_sigma [B][ndx], rng_wsigma [B][6] (pl_mpc_set_noise, null: that stream off):
+// this step's fresh draw of the state noise and of the base wrench (noise.h).
 // keys (pl_mpc_set_timeline, null: none): [B][n_key] keyframes, count [B] of them valid, tls [B]
 // what this launch used.  With a timeline the problem's commands, gait scalars and schedule come
 // from its governing keyframe (timeline.h) instead of the handle's one gait; the warm start below
@@ -410,32 +413,37 @@ void launch_line_search(PlOcpHandle* h) {
 __global__ __launch_bounds__(64) void k_mpc_prepare(PlDev d, int k, int N, int n, int np, int nx, int gait_type,
                                                     double period, double swing_period, const double* noise,
                                                     const int* push_k, const double* push_w, const PlKeyframe* keys,
-                                                    int n_key, const int* count, PlTimelineState* tls) {
+                                                    int n_key, const int* count, PlTimelineState* tls,
+                                                    const unsigned long long* rng_seed, const double* rng_sigma,
+                                                    const double* rng_wsigma) {
   const int b = blockIdx.x;
   const PlOcpConst& O = *d.oc;
   const PlModel& M = *d.model;
   double* p = d.p + (size_t)b * np;
-  // push schedule (pl_mpc_set_push, null: none): the plant's base wrench of this step is the
-  // problem's wrench inside its window [k_start, k_end) and zero outside; k_plant reads it as ever
-  if (push_k && threadIdx.x < 6) {
-    const bool in = push_k[b] <= k && k < push_k[gridDim.x + b];
-    d.plant_w[(size_t)b * 6 + threadIdx.x] = in ? push_w[(size_t)b * 6 + threadIdx.x] : 0.0;
+  // base wrench of this step, which k_plant reads as ever.  Push schedule (pl_mpc_set_push, null:
+  // none): the problem's wrench inside its window [k_start, k_end), zero outside.  Random wrench
+  // (pl_mpc_set_noise, null: none): lane c adds its draw, window_c + sigma_w,c z_c (noise.h).
+  if ((push_k || rng_wsigma) && threadIdx.x < 6) {
+    const int c = threadIdx.x;
+    double w = 0.0;
+    if (push_k) {
+      const bool in = push_k[b] <= k && k < push_k[gridDim.x + b];
+      w = in ? push_w[(size_t)b * 6 + c] : 0.0;
+    }
+    if (rng_wsigma) w = pl::noise_wrench(rng_seed[b], k, c, w, rng_wsigma[(size_t)b * 6 + c]);
+    d.plant_w[(size_t)b * 6 + c] = w;
+  }
+  // random state noise (null: none): lane j draws sigma_j z_j into d.plant_noise, which `noise` is
+  // then; lane 0 integrates it below
+  if (rng_sigma) {
+    for (int j = threadIdx.x; j < O.ndx; j += blockDim.x)
+      d.plant_noise[(size_t)b * O.ndx + j] = pl::noise_state(rng_seed[b], k, j, rng_sigma[(size_t)b * O.ndx + j]);
+    __syncthreads();
   }
   if (!noise) {
     for (int j = threadIdx.x; j < nx; j += blockDim.x) p[O.P.x_init + j] = d.xstate[(size_t)b * nx + j];
   } else if (threadIdx.x == 0) {
-    const double* xs = d.xstate + (size_t)b * nx;
-    const double* nb = noise + (size_t)b * O.ndx;
-    double* xi = p + O.P.x_init;
-    if (PL_IS_CV(O.dyn)) {  // x = [h, q] (dynamics_centroidal_vel.py:12-26)
-      VecIn<double> acc{nb + 6, nullptr, 0.0, -1};
-      for (int j = 0; j < 6; ++j) xi[j] = xs[j] + nb[j];
-      pl::integrate_q<double>(M, xs + 6, acc, xi + 6);
-    } else {
-      VecIn<double> acc{nb, nullptr, 0.0, -1};
-      pl::integrate_q<double>(M, xs, acc, xi);
-      for (int j = 0; j < O.nv; ++j) xi[O.nq + j] = xs[O.nq + j] + nb[O.nv + j];
-    }
+    pl::noise_x_init(M, O, d.xstate + (size_t)b * nx, noise + (size_t)b * O.ndx, p + O.P.x_init);
   }
   double t_shift = 0.0;
   if (keys) {
@@ -500,9 +508,29 @@ __global__ void k_mpc_finish(PlDev d, int B, int n, int nx) {
 void launch_mpc_prepare(PlOcpHandle* h, int k) {
   hipLaunchKernelGGL(k_mpc_prepare, dim3(h->B), dim3(64), 0, h->stream, h->d, k, h->N, h->n, h->np, h->nx,
                      h->gait_type, h->gait_period, h->swing_period,
-                     h->plant_noise_on ? (const double*)h->d.plant_noise : nullptr,
+                     h->plant_noise_on || h->rng_state_on ? (const double*)h->d.plant_noise : nullptr,
                      h->push_on ? (const int*)h->push_k : nullptr, (const double*)h->push_w,
-                     h->tl_on ? (const PlKeyframe*)h->tl_keys : nullptr, h->tl_nkey, (const int*)h->tl_count, h->tl_state);
+                     h->tl_on ? (const PlKeyframe*)h->tl_keys : nullptr, h->tl_nkey, (const int*)h->tl_count, h->tl_state,
+                     (const unsigned long long*)h->rng_seed, h->rng_state_on ? (const double*)h->rng_sigma : nullptr,
+                     h->rng_wrench_on ? (const double*)h->rng_wsigma : nullptr);
+}
+
+// The raw Philox blocks of the problems' seeds (pl_debug_rng): block i of problem b has the
+// counter (k, i0 + i, stream, c3); out [B][n_blocks][4] words.
+__global__ __launch_bounds__(64) void k_rng_blocks(const unsigned long long* seed, uint32_t k, uint32_t stream,
+                                                   uint32_t i0, uint32_t c3, int n_blocks, uint32_t* out) {
+  const int b = blockIdx.x;
+  for (int i = threadIdx.x; i < n_blocks; i += blockDim.x) {
+    uint32_t w[4];
+    pl::rng_block(seed[b], k, i0 + (uint32_t)i, stream, c3, w);
+    for (int j = 0; j < 4; ++j) out[((size_t)b * n_blocks + i) * 4 + j] = w[j];
+  }
+}
+
+void launch_rng_blocks(PlOcpHandle* h, unsigned k, unsigned stream, unsigned i0, unsigned c3, int n_blocks,
+                       unsigned* out) {
+  hipLaunchKernelGGL(k_rng_blocks, dim3(h->B), dim3(64), 0, h->stream, (const unsigned long long*)h->rng_seed, k, stream,
+                     i0, c3, n_blocks, out);
 }
 
 void launch_mpc_finish(PlOcpHandle* h) {

@@ -416,6 +416,15 @@ struct PlOcpHandle {
   struct PlKeyframe* tl_keys;        // [B][tl_nkey]
   int* tl_count;                     // [B] valid keyframes of each problem
   struct PlTimelineState* tl_state;  // [B] what the last prepare launch used
+  // Per-step random state noise and base wrench (pl_mpc_set_noise, noise.h): drawn by
+  // k_mpc_prepare alone into d.plant_noise / d.plant_w, so outside the key like the push schedule;
+  // switching a stream on or off or giving new seeds or sigmas never re-captures.
+  int rng_state_on;                  // 1: k_mpc_prepare draws d.plant_noise and plans from the measured state
+  int rng_wrench_on;                 // 1: k_mpc_prepare writes d.plant_w = window's wrench + sigma_w z
+  int dist_wrench_on;                // 1 while a base_wrench of pl_mpc_set_disturbance is what d.plant_w holds
+  unsigned long long* rng_seed;      // [B]
+  double* rng_sigma;                 // [B][ndx]
+  double* rng_wsigma;                // [B][6]
 };
 
 // ---- kernel launchers (defined in the k_*.hip translation units)
@@ -458,6 +467,9 @@ void launch_unscale(PlOcpHandle* h);
 void launch_line_search(PlOcpHandle* h);
 void launch_mpc_prepare(PlOcpHandle* h, int k);
 void launch_mpc_finish(PlOcpHandle* h);
+// pl_debug_rng: block i of problem b at the counter (k, i0 + i, stream, c3), out [B][n_blocks][4] on the device
+void launch_rng_blocks(PlOcpHandle* h, unsigned k, unsigned stream, unsigned i0, unsigned c3, int n_blocks,
+                       unsigned* out);
 void launch_plant(PlOcpHandle* h);  // k_plant.hip
 void launch_mpc_record(PlOcpHandle* h, int k, long long slot, int nu0);  // k_record.hip
 void launch_mpc_record_start(PlOcpHandle* h);

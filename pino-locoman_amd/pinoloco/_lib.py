@@ -90,6 +90,8 @@ timeline_dtype = np.dtype([("k_start", np.int32), ("gait_type", np.int32), ("ram
 assert timeline_dtype.itemsize == C.sizeof(Keyframe) == 128
 
 _llp = C.POINTER(C.c_longlong)
+_u64p = C.POINTER(C.c_ulonglong)
+_u32p = C.POINTER(C.c_uint)
 
 EXPORTS = {
     "pl_last_error": (C.c_char_p, []),
@@ -163,6 +165,13 @@ EXPORTS = {
     "pl_mpc_get_timeline": (C.c_int, [C.c_void_p, _ip, _ip]),
     "pl_mpc_timeline_state": (C.c_int, [C.c_void_p, _ip, _ip, _dp, _dp]),
     "pl_mpc_timeline_host": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(Keyframe), C.c_int, _dp, _dp, _ip]),
+    "pl_mpc_set_noise": (C.c_int, [C.c_void_p, _u64p, _dp, _dp]),
+    "pl_mpc_get_noise": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "pl_mpc_noise_state": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "pl_mpc_noise_host": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pl_rng_block_host": (C.c_int, [_u32p, _u32p, _u32p]),
+    "pl_rng_uniforms_host": (C.c_int, [_u32p, _dp, _dp]),
+    "pl_debug_rng": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, _u32p]),
     "pl_ocp_sync": (C.c_int, [C.c_void_p]),
     "pl_state_integrate": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "pl_state_difference": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),

@@ -540,7 +540,8 @@ class BatchedOCP:
         base_wrench [batch][6]: generalised force on v[0:6] of the free-flyer (linear then angular,
         base frame), applied by the "aba" plant.  state_noise [batch][ndx]: the MPC plans from
         x_init = state_integrate(x_state, noise) (run_mpc.py:79-82); mpc_state() stays the true
-        state.  New values replay the captured step; the caller draws the noise."""
+        state.  New values replay the captured step.  The vectors hold as given: for a fresh draw at
+        every step, made on the device, see mpc_set_noise."""
         def arr(a, width, name):
             if a is None:
                 return None
@@ -736,6 +737,111 @@ class BatchedOCP:
     def mpc_run(self, k0, steps):
         """mpc_step(k0) ... mpc_step(k0 + steps - 1), enqueued back to back (pl_mpc_run)."""
         _lib.check(_lib.lib().pl_mpc_run(self.h, int(k0), int(steps)))
+
+    # ---------------------------------------------------------------- per-step random noise
+    @staticmethod
+    def _seeds(seed, count):
+        """[count] uint64 from a scalar or an array of non-negative integers below 2**64."""
+        try:
+            s = np.asarray(seed, dtype=np.uint64)
+        except (OverflowError, TypeError, ValueError) as exc:
+            raise _lib.PinolocoError(f"seed: {exc}") from exc
+        if s.shape not in ((), (count,)):
+            raise _lib.PinolocoError(f"seed has shape {s.shape}, expected a scalar or {(count,)}")
+        return np.ascontiguousarray(np.broadcast_to(s, (count,)))
+
+    def mpc_set_noise(self, seed=None, state_sigma=None, wrench_sigma=None):
+        """Fresh Gaussian noise at every MPC step, drawn on the device (pl_mpc_set_noise): step k
+        plans from x_init = state_integrate(x_state, state_sigma * z) (run_mpc.py:79-82) and the
+        "aba" plant runs with the base wrench (push window's wrench or 0) + wrench_sigma * z.  z is
+        a pure function of (seed[b], stream, k, component): the same in any batch, slot or shard
+        (synthetic.noise_seeds), and the same whether the steps come from mpc_run or one by one.
+        seed: [batch] integers below 2**64; state_sigma: a scalar, [ndx] or [batch][ndx], None
+        leaves that stream off; wrench_sigma: a scalar, [6] or [batch][6], None likewise.
+        seed=None switches both off.  Exclusive with the matching argument of
+        mpc_set_disturbance; combines with mpc_set_push.  Never re-captures the step's graph."""
+        if seed is None:
+            if state_sigma is not None or wrench_sigma is not None:
+                raise _lib.PinolocoError("mpc_set_noise: sigmas without seeds")
+            _lib.check(_lib.lib().pl_mpc_set_noise(self.h, None, None, None))
+            return
+        s = self._seeds(seed, self.batch)
+        sig = self._sigma(state_sigma, "state_sigma", self.batch, self.layout.ndx)
+        wsig = self._sigma(wrench_sigma, "wrench_sigma", self.batch, 6)
+        _lib.check(_lib.lib().pl_mpc_set_noise(self.h, s.ctypes.data_as(_lib._u64p),
+                                               None if sig is None else _lib.dptr(sig),
+                                               None if wsig is None else _lib.dptr(wsig)))
+
+    @staticmethod
+    def _sigma(a, name, count, width):
+        """None, or a contiguous [count][width] array from a scalar, [width] or [count][width]."""
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape not in ((), (width,), (count, width)):
+            raise _lib.PinolocoError(f"{name} has shape {a.shape}, expected a scalar, {(width,)} or {(count, width)}")
+        return np.ascontiguousarray(np.broadcast_to(a, (count, width)))
+
+    def mpc_get_noise(self):
+        """{"state": bool, "wrench": bool}: which random streams are on."""
+        s, w = C.c_int(), C.c_int()
+        _lib.check(_lib.lib().pl_mpc_get_noise(self.h, C.byref(s), C.byref(w)))
+        return {"state": bool(s.value), "wrench": bool(w.value)}
+
+    def mpc_noise_state(self):
+        """(state_noise [batch][ndx], base_wrench [batch][6]) the last gait / warm-start launch
+        planned with: the drawn values while a stream is on (pl_mpc_noise_state)."""
+        z, w = np.zeros((self.batch, self.layout.ndx)), np.zeros((self.batch, 6))
+        _lib.check(_lib.lib().pl_mpc_noise_state(self.h, _lib.dptr(z), _lib.dptr(w)))
+        return z, w
+
+    def mpc_noise_host(self, k, seed, state_sigma=None, wrench_sigma=None, det_wrench=None, x_state=None):
+        """One problem's draw of step k and its x_init on the host, the code the kernel runs
+        (pl_mpc_noise_host): seed an integer; state_sigma a scalar or [ndx], wrench_sigma a scalar
+        or [6] (None: that stream off); det_wrench [6] the step's deterministic wrench (None:
+        zero); x_state [nx] (None: no x_init).  Returns (state_noise [ndx], base_wrench [6],
+        x_init [nx] or None).  Needs no device."""
+        s = self._seeds(seed, 1)
+        sig = self._sigma(state_sigma, "state_sigma", 1, self.layout.ndx)
+        wsig = self._sigma(wrench_sigma, "wrench_sigma", 1, 6)
+        det = self._sigma(det_wrench, "det_wrench", 1, 6)
+        xs = xi = None
+        if x_state is not None:
+            xs = np.ascontiguousarray(np.asarray(x_state, dtype=np.float64))
+            if xs.shape != (self.layout.nx,):
+                raise _lib.PinolocoError(f"x_state has shape {xs.shape}, expected {(self.layout.nx,)}")
+            xi = np.zeros(self.layout.nx)
+        z, w = np.zeros(self.layout.ndx), np.zeros(6)
+        opt = lambda a: None if a is None else _lib.dptr(a)
+        _lib.check(_lib.lib().pl_mpc_noise_host(self.h, int(k), int(s[0]), opt(sig), opt(wsig), opt(det), opt(xs),
+                                                _lib.dptr(z), _lib.dptr(w), opt(xi)))
+        return z, w, xi
+
+    @staticmethod
+    def rng_block_host(ctr, key):
+        """One Philox4x32-10 block on the host (pl_rng_block_host): ctr [4], key [2] -> [4] uint32."""
+        c = np.ascontiguousarray(np.asarray(ctr, dtype=np.uint32).reshape(4))
+        k = np.ascontiguousarray(np.asarray(key, dtype=np.uint32).reshape(2))
+        out = np.zeros(4, dtype=np.uint32)
+        _lib.check(_lib.lib().pl_rng_block_host(c.ctypes.data_as(_lib._u32p), k.ctypes.data_as(_lib._u32p),
+                                                out.ctypes.data_as(_lib._u32p)))
+        return out
+
+    @staticmethod
+    def rng_uniforms_host(words):
+        """(u1, theta) of one block's words [4] on the host (pl_rng_uniforms_host)."""
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).reshape(4))
+        u1, th = C.c_double(), C.c_double()
+        _lib.check(_lib.lib().pl_rng_uniforms_host(w.ctypes.data_as(_lib._u32p), C.byref(u1), C.byref(th)))
+        return u1.value, th.value
+
+    def debug_rng(self, k, stream, n_blocks, i0=0, c3=0):
+        """Stage tests: the device's raw Philox blocks for the seeds of mpc_set_noise (pl_debug_rng),
+        [batch][n_blocks][4] uint32: block i of problem b at the counter (k, i0 + i, stream, c3)."""
+        out = np.zeros((self.batch, max(int(n_blocks), 0), 4), dtype=np.uint32)
+        _lib.check(_lib.lib().pl_debug_rng(self.h, int(k), int(stream), int(i0), int(c3), int(n_blocks),
+                                           out.ctypes.data_as(_lib._u32p)))
+        return out
 
     # ---------------------------------------------------------------- gait and command timelines
     KEYFRAME_FIELDS = ("k_start", "gait_type", "ramp", "gait_period", "t_shift", "base_vel_des", "ext_force_des",

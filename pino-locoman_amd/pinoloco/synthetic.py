@@ -103,6 +103,14 @@ def build_batch(robot, dynamics, N, B, first=0, include_base=True, include_acc=T
     return lay, P, X, XS, T0
 
 
+def noise_seeds(first, count):
+    """Seeds of the per-step random noise (BatchedOCP.mpc_set_noise) for the problems at global
+    indices [first, first + count): 1234 + global index, as random_state seeds the problem itself.
+    With ``first, count = shard(global_batch, world, rank)`` a problem draws the noise it draws in
+    the single-GPU run."""
+    return np.uint64(1234) + np.arange(first, first + count, dtype=np.uint64)
+
+
 def shard(global_batch, world, rank):
     """Contiguous shard [first, first + count) of rank ``rank``."""
     base, rem = divmod(global_batch, world)
